@@ -6,8 +6,14 @@ Metric (BASELINE.json): "SpGEMM+SSpMM edges/sec on Reddit, hidden=256, k in {8,1
 all E edges, inputs (graph, CBSR features, upstream gradient) resident in HBM;
 value = 2E / step time (edges/s = 2E / (t_fwd + t_bwd)).
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (N > 1)
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value,
+ms_per_step, configuration, topology). --dump-outputs DIR also writes what the last timed step
+returned (DIR/out.npy, DIR/grad_sp.npy). --full adds everything that takes runs of its own:
+per-kernel device times and the roofline, the exchange times (N > 1), the top-k producer, the
+k sweep, the rocSPARSE comparator and the CPU baseline.
 
 N > 1: the rows are partitioned over the ranks (strong scaling: the Reddit graph is fixed)
 and each step includes the RCCL all-gather of the CBSR records and the reduce-scatter of
@@ -92,6 +98,35 @@ def launch_percentiles_ms(fn, reps):
     t = sorted(s.elapsed_time(e) for s, e in evs)
     pick = lambda q: t[min(len(t) - 1, int(round(q * (len(t) - 1))))]  # noqa: E731
     return {"p10": pick(0.1), "median": pick(0.5), "p90": pick(0.9)}
+
+
+DUMP_BUDGET_BYTES = 60 << 20   # all dumped arrays of all ranks together: under 64 MB
+
+
+def dump_rows(num_rows, num_cols, share):
+    """The rows of a float32 [num_rows, num_cols] array that a dump of at most ``share`` bytes
+    keeps: None (all of them) when it fits, else a sorted sample drawn from a fixed seed."""
+    import numpy
+    keep = max(1, share // (4 * num_cols))
+    if num_rows <= keep:
+        return None
+    return numpy.sort(numpy.random.default_rng(97).choice(num_rows, keep, replace=False))
+
+
+def dump_outputs(dirname, arrays, rank, world):
+    """--dump-outputs: the arrays the last timed step returned, as DIR/<name>.npy (float32;
+    DIR/<name>.rank<R>.npy for N > 1). An array larger than its share of the budget is cut to
+    the rows :func:`dump_rows` picks: the same rows in every run and every build, so two dumps
+    compare element for element."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // (len(arrays) * world)
+    for name, t in arrays.items():
+        pick = dump_rows(t.shape[0], t.shape[1], share)
+        if pick is not None:
+            t = t[torch.from_numpy(pick).to(t.device)]
+        suffix = f".rank{rank}" if world > 1 else ""
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"),
+                t.detach().to(torch.float32).cpu().numpy())
 
 
 def cpu_model():
@@ -214,6 +249,12 @@ def parse_args(argv=None):
                     help="'synthetic', 'auto' (the DGL cache file ~/.dgl/... when it exists, "
                          "else synthetic) or a path to a scipy save_npz adjacency")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"))
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: per-kernel times and "
+                         "roofline, exchange times, top-k, k sweep, comparator, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32; rows "
+                         "of a large output are a fixed, seeded sample)")
     return ap.parse_args(argv)
 
 
@@ -516,6 +557,7 @@ def run(args):
         def step():
             fwd()
             bwd()
+            return out, grad_sp
     else:
         def build_shard():
             sh = ShardedAggregation(part, rank, ptr, idx, val, d, k, local_edges=True)
@@ -535,8 +577,7 @@ def run(args):
             shard.compute_backward(g)
 
         def step():
-            shard.forward(sp_data, sp_index)
-            shard.backward(g)
+            return shard.forward(sp_data, sp_index), shard.backward(g)
     torch.cuda.synchronize()
     plan_s = time.perf_counter() - t0
     log(f"plan built in {plan_s:.2f}s: {info}")
@@ -549,8 +590,9 @@ def run(args):
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last = None
     for _ in range(args.steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -562,6 +604,44 @@ def run(args):
         elapsed = float(tt.item())
     ms_per_step = elapsed * 1e3 / args.steps
     value = 2.0 * e / (elapsed / args.steps)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"out": last[0], "grad_sp": last[1]}, rank, world)
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
+
+    result = {
+        "metric": METRIC,
+        "value": value,
+        "unit": "edges/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": data,
+        "config": {
+            "workload": f"{args.dataset} SpGEMM fwd + SSpMM bwd over CBSR (MaxK exact), "
+                        f"D={d}, k={k}",
+            "dataset": args.dataset, "num_nodes": n, "num_edges": e, "dim_origin": d,
+            "dim_k": k,
+            "parallelism": "single-gpu" if world == 1 else
+            f"row-partition x{world} + {'RCCL' if backend == 'nccl' else 'gloo (rehearsal)'} "
+            f"all-gather(CBSR records) / reduce-scatter(grad_sp)",
+        },
+        "plan_build_s": plan_s,
+        "topology": topology,
+        "full": args.full,
+    }
+    if not args.full:
+        # a plain run: the headline figure alone
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # per-kernel device time (HIP events on the launch stream), this rank's shard
     reps = max(5, args.steps)
@@ -621,28 +701,7 @@ def run(args):
     if traffic_stale:
         traffic, detail = None, {}
 
-    result = {
-        "metric": METRIC,
-        "value": value,
-        "unit": "edges/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": data,
-        "config": {
-            "workload": f"{args.dataset} SpGEMM fwd + SSpMM bwd over CBSR (MaxK exact), "
-                        f"D={d}, k={k}",
-            "dataset": args.dataset, "num_nodes": n, "num_edges": e, "dim_origin": d,
-            "dim_k": k,
-            "parallelism": "single-gpu" if world == 1 else
-            f"row-partition x{world} + {'RCCL' if backend == 'nccl' else 'gloo (rehearsal)'} "
-            f"all-gather(CBSR records) / reduce-scatter(grad_sp)",
-        },
+    result.update({
         "roofline": {
             "bound": "hbm",
             "kernel": dom,
@@ -677,10 +736,8 @@ def run(args):
         "bwd_edges_per_s": e_loc / (bwd_ms * 1e-3),
         "fwd_roofline_frac": fwd_gbs / HBM_PEAK_GBS,
         "bwd_roofline_frac": bwd_gbs / HBM_PEAK_GBS,
-        "plan_build_s": plan_s,
-        "topology": topology,
         "cpu_baseline": None,
-    }
+    })
 
     def sweep_traffic(ks, tf, tb):
         """PMC traffic (FETCH_SIZE x 2 + WRITE_SIZE per launch, profiles/pmc_traffic.json) of

@@ -5,6 +5,7 @@ copies); fp32 accumulators within 1e-5 relative: plain |got - ref| <= 1e-5 |ref|
 element that does not cancel (|ref| >= half the sum of its |terms|), 1e-5 of that sum on
 the ones that do (oracle.close_enough).
 """
+import glob
 import os
 
 import numpy as np
@@ -17,14 +18,20 @@ from oracle import oracle
 
 pytestmark = pytest.mark.gpu
 
-GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "maxk_small.npz")
+# one set of arrays, committed in parts (tests/golden/make_golden.py:write_parts)
+GOLDEN = sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden",
+                                       "maxk_small.part*.npz")))
 RTOL = 1e-5
 
 
 @pytest.fixture(scope="module")
 def golden():
-    with np.load(GOLDEN, allow_pickle=False) as z:
-        return {k: z[k] for k in z.files}
+    assert GOLDEN, "tests/golden/maxk_small.part*.npz missing"
+    out = {}
+    for path in GOLDEN:
+        with np.load(path, allow_pickle=False) as z:
+            out.update({k: z[k] for k in z.files})
+    return out
 
 
 def to_dev(a, dev, dtype=None):

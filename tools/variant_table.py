@@ -1,7 +1,7 @@
-"""Summarise bench.py logs of library variants (tooling): for each gpurun_out/<name>.log given,
+"""Summarise `bench.py --full` logs of library variants (tooling): for each log file given,
 the per-k forward / backward times of its last JSON line.
 
-  python tools/variant_table.py gpurun_out/v_base.log gpurun_out/v_x.log ...
+  python tools/variant_table.py v_base.log v_x.log ...
 """
 import json
 import sys
