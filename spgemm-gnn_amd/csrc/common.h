@@ -118,6 +118,30 @@ inline int cbsr_record_bytes(int k) {
   return b <= 64 ? 64 : b <= 128 ? 128 : (b + 15) / 16 * 16;
 }
 
+// Forward records handed over by the caller (maxk_topk_cbsr_records writes them,
+// maxk_spgemm_forward_records gathers them): layout as maxk_plan_info.fwd_layout 1, 2 or 4, one
+// record every record_bytes from a 16-B aligned base. `need`: a null base is an error.
+inline int check_records(const void* records, int64_t record_bytes, int layout, int k, bool need,
+                         const char* who) {
+  const std::string w(who);
+  if (layout != 1 && layout != 2 && layout != 4) {
+    set_error(w + ": layout must be 1, 2 or 4 (maxk_plan_info.fwd_layout)");
+    return MAXK_ERR_UNSUPPORTED;
+  }
+  MAXK_CHECK_ARG(layout != 1 || k % 4 == 0, w + ": layout 1 needs k % 4 == 0");
+  MAXK_CHECK_ARG(layout != 2 || (k + 2) / 3 <= kWave, w + ": layout 2 needs (k + 2) / 3 <= 64");
+  MAXK_CHECK_ARG(layout != 4 || (k % 2 == 0 && k / 2 <= kWave),
+                 w + ": layout 4 needs an even k with k / 2 <= 64");
+  const int64_t bytes = layout == 1 ? 5 * (int64_t)k : 16 * (int64_t)((k + (layout == 2 ? 2 : 1)) /
+                                                                      (layout == 2 ? 3 : 2));
+  MAXK_CHECK_ARG(record_bytes % 16 == 0 && record_bytes >= bytes && record_bytes <= INT32_MAX,
+                 w + ": record_bytes must be a multiple of 16 that holds the row's record");
+  MAXK_CHECK_ARG((reinterpret_cast<uintptr_t>(records) & 15) == 0,
+                 w + ": records must be 16-B aligned");
+  MAXK_CHECK_ARG(records || !need, w + ": records is null");
+  return MAXK_OK;
+}
+
 // Backward work item: edges [e0, e1) of the column-block-major, row-sorted edge list, all
 // with source column in [col0, col0 + ncols). shared != 0: the block is split over several
 // work-groups, so its LDS accumulator is flushed with float atomics into a pre-zeroed
@@ -244,3 +268,11 @@ struct maxk_plan {
   int32_t fwd_handout = 1;
   int32_t bwd_handout = 1;
 };
+
+// maxk_plan_info.fwd_layout: what the plan's forward gathers from (maxk_hip.h).
+inline int plan_fwd_layout(const maxk_plan* p) {
+  if (p->fwd_chunk2) return 4;
+  if (p->fwd_chunk3) return 2;
+  if (p->dim_k % 4 != 0) return 3;
+  return p->fwd_two_tables ? 0 : 1;
+}

@@ -1526,18 +1526,10 @@ extern "C" int maxk_plan_get_info_sized(const maxk_plan* p, maxk_plan_info* out,
   info.fwd_unroll = p->fwd_unroll;
   info.bwd_waves = p->bwd_twopass ? 0 : p->bwd_waves;  // the two-pass kernels have one shape
   info.bwd_unroll = p->bwd_twopass ? 0 : p->bwd_unroll;
-  if (p->fwd_chunk2) {
-    info.fwd_layout = 4;
+  info.fwd_layout = plan_fwd_layout(p);
+  if (info.fwd_layout == 1 || info.fwd_layout == 2 || info.fwd_layout == 4)
     info.fwd_record_bytes = p->fwd_rec_bytes;
-  } else if (p->fwd_chunk3) {
-    info.fwd_layout = 2;
-    info.fwd_record_bytes = p->fwd_rec_bytes;
-  } else if (p->dim_k % 4 != 0) {
-    info.fwd_layout = 3;
-  } else if (!p->fwd_two_tables) {
-    info.fwd_layout = 1;
-    info.fwd_record_bytes = p->fwd_rec_bytes;
-  }
+  info.fwd_fixed = p->fwd_fix && p->num_cols > 0 ? 1 : 0;
   std::memcpy(out, &info, (size_t)std::min<int64_t>(info_bytes, (int64_t)sizeof(maxk_plan_info)));
   return MAXK_OK;
 }

@@ -1232,6 +1232,54 @@ static int table_strides(int64_t& ds, int64_t& is, int k, const char* who) {
   return MAXK_OK;
 }
 
+// The forward kernel's launch, shared by the table entry points (spgemm_forward_impl: recp is
+// the per-call pack, or the caller's tables) and maxk_spgemm_forward_records (recp is the
+// caller's records; sp_data / sp_index null: only the one-feature-per-lane kernel, which no
+// record layout runs, reads them).
+static int launch_spgemm_fwd(const maxk_plan* plan, const float* sp_data, int ds,
+                             const uint8_t* sp_index, int is, const uint8_t* recp, int rec_bytes,
+                             const uint8_t* seltab, float* out, int D, int k, int accum,
+                             const int2* fix_tab, const uint32_t* xstat, int xs_n, int xs_stride,
+                             int xs_off2, size_t lds, hipStream_t s) {
+  const bool pairs = plan->fwd_chunk2;
+  if (plan->n_fwd_tasks == 0) return MAXK_OK;
+  const int Lf = plan->fwd_chunk3 ? (k + 2) / 3 : pairs ? k / 2 : k / 4;  // lanes per edge
+  const int FL = (plan->fwd_chunk3 ? kFwdFlagChunk3 : 0) | (pairs ? kFwdFlagChunk2 : 0) |
+                 (plan->fwd_quad && Lf % 4 == 0 ? kFwdFlagQuad : 0);
+  const int fwaves = plan->fwd_waves;
+#define FWD_LAUNCH_NT(V, FF, NT, FU)                                                        \
+  do {                                                                                      \
+    if (lds > 64 * 1024) MAXK_HIP_TRY(allow_lds(spgemm_fwd_kernel<V, FF, NT, FU>, lds));     \
+    hipLaunchKernelGGL((spgemm_fwd_kernel<V, FF, NT, FU>), dim3(plan->n_fwd_tasks), dim3(NT), \
+                       lds, s, plan->fwd_tasks, plan->fwd_phase_off, plan->fwd_phases,      \
+                       plan->fwd_cv, sp_data, sp_index, recp, rec_bytes, out, D, k,         \
+                       plan->fwd_rot_ticks, seltab, is, ds, accum, fix_tab, xstat, xs_n,     \
+                       xs_stride, xs_off2, plan->fwd_handout == 2 ? 1 : 0);                 \
+  } while (0)
+#define FWD_LAUNCH(V, FF)                                                                   \
+  do {                                                                                      \
+    if (fwaves == 8 && plan->fwd_unroll == 4) FWD_LAUNCH_NT(V, FF, 8 * kWave, 4);            \
+    else if (fwaves == 8) FWD_LAUNCH_NT(V, FF, 8 * kWave, kFwdUnroll);                      \
+    else FWD_LAUNCH_NT(V, FF, kFwdThreads, kFwdUnroll);                                     \
+  } while (0)
+  if (k % 4 == 0 || plan->fwd_chunk3 || plan->fwd_chunk2) {
+    switch (FL) {
+      case 0: FWD_LAUNCH(4, 0); break;
+      case kFwdFlagChunk3: FWD_LAUNCH(4, kFwdFlagChunk3); break;
+      case kFwdFlagQuad: FWD_LAUNCH(4, kFwdFlagQuad); break;
+      case kFwdFlagChunk2: FWD_LAUNCH(4, kFwdFlagChunk2); break;
+      case kFwdFlagChunk2 | kFwdFlagQuad: FWD_LAUNCH(4, kFwdFlagChunk2 | kFwdFlagQuad); break;
+      default: FWD_LAUNCH(4, kFwdFlagChunk3 | kFwdFlagQuad); break;
+    }
+  } else {
+    FWD_LAUNCH(1, 0);
+  }
+#undef FWD_LAUNCH
+#undef FWD_LAUNCH_NT
+  MAXK_LAUNCH_CHECK("spgemm_fwd launch");
+  return MAXK_OK;
+}
+
 static int spgemm_forward_impl(const maxk_plan* plan, const int32_t* ptr, const int32_t* idx,
                                const float* val, const float* sp_data, int64_t ds64,
                                const uint8_t* sp_index, int64_t is64, float* out, int32_t N,
@@ -1325,42 +1373,8 @@ static int spgemm_forward_impl(const maxk_plan* plan, const int32_t* ptr, const 
                                       plan->zero_rows, zero_in_stats ? nz : 0, out, D, pairs);
     if (rc2) return rc2;
   }
-  if (plan->n_fwd_tasks == 0) return MAXK_OK;
-  const int Lf = plan->fwd_chunk3 ? (k + 2) / 3 : pairs ? k / 2 : k / 4;  // lanes per edge
-  const int FL = (plan->fwd_chunk3 ? kFwdFlagChunk3 : 0) | (pairs ? kFwdFlagChunk2 : 0) |
-                 (plan->fwd_quad && Lf % 4 == 0 ? kFwdFlagQuad : 0);
-  const int fwaves = plan->fwd_waves;
-#define FWD_LAUNCH_NT(V, FF, NT, FU)                                                        \
-  do {                                                                                      \
-    if (lds > 64 * 1024) MAXK_HIP_TRY(allow_lds(spgemm_fwd_kernel<V, FF, NT, FU>, lds));     \
-    hipLaunchKernelGGL((spgemm_fwd_kernel<V, FF, NT, FU>), dim3(plan->n_fwd_tasks), dim3(NT), \
-                       lds, s, plan->fwd_tasks, plan->fwd_phase_off, plan->fwd_phases,      \
-                       plan->fwd_cv, sp_data, sp_index, recp, rec_bytes, out, D, k,         \
-                       plan->fwd_rot_ticks, seltab, is, ds, accum, fix_tab, xstat, xs_n,     \
-                       xs_stride, xs_off2, plan->fwd_handout == 2 ? 1 : 0);                 \
-  } while (0)
-#define FWD_LAUNCH(V, FF)                                                                   \
-  do {                                                                                      \
-    if (fwaves == 8 && plan->fwd_unroll == 4) FWD_LAUNCH_NT(V, FF, 8 * kWave, 4);            \
-    else if (fwaves == 8) FWD_LAUNCH_NT(V, FF, 8 * kWave, kFwdUnroll);                      \
-    else FWD_LAUNCH_NT(V, FF, kFwdThreads, kFwdUnroll);                                     \
-  } while (0)
-  if (k % 4 == 0 || plan->fwd_chunk3 || plan->fwd_chunk2) {
-    switch (FL) {
-      case 0: FWD_LAUNCH(4, 0); break;
-      case kFwdFlagChunk3: FWD_LAUNCH(4, kFwdFlagChunk3); break;
-      case kFwdFlagQuad: FWD_LAUNCH(4, kFwdFlagQuad); break;
-      case kFwdFlagChunk2: FWD_LAUNCH(4, kFwdFlagChunk2); break;
-      case kFwdFlagChunk2 | kFwdFlagQuad: FWD_LAUNCH(4, kFwdFlagChunk2 | kFwdFlagQuad); break;
-      default: FWD_LAUNCH(4, kFwdFlagChunk3 | kFwdFlagQuad); break;
-    }
-  } else {
-    FWD_LAUNCH(1, 0);
-  }
-#undef FWD_LAUNCH
-#undef FWD_LAUNCH_NT
-  MAXK_LAUNCH_CHECK("spgemm_fwd launch");
-  return MAXK_OK;
+  return launch_spgemm_fwd(plan, sp_data, ds, sp_index, is, recp, rec_bytes, seltab, out, D, k,
+                           accum, fix_tab, xstat, xs_n, xs_stride, xs_off2, lds, s);
 }
 
 extern "C" int maxk_spgemm_forward(const maxk_plan* plan, const int32_t* ptr,
@@ -1411,6 +1425,59 @@ extern "C" int maxk_spgemm_forward_tables(const maxk_plan* plan, const int32_t* 
   return spgemm_forward_impl(plan, ptr, idx, val, sp_data, data_stride, sp_index, index_stride,
                              out, N, E, k, D, stream, accumulate, workspace, workspace_bytes,
                              stats, n_stats, stats_stride);
+}
+
+// The forward from the caller's records (maxk_topk_cbsr_records): the kernel launch alone, plus
+// zero_rows when the plan splits rows. No pack, no statistics pass, no memset, no workspace.
+extern "C" int maxk_spgemm_forward_records(const maxk_plan* plan, const int32_t* ptr,
+                                           const int32_t* idx, const float* val,
+                                           const void* records, int64_t record_bytes,
+                                           int32_t layout, float* out, int32_t N, int64_t E,
+                                           int32_t k, int32_t D, int32_t accumulate,
+                                           const uint32_t* stats, int32_t n_stats,
+                                           int64_t stats_stride, void* stream) {
+  const char* who = "maxk_spgemm_forward_records";
+  MAXK_CHECK_ARG(accumulate == 0 || accumulate == 1,
+                 std::string(who) + ": accumulate must be 0 or 1");
+  MAXK_CHECK_ARG(N >= 0 && E >= 0, std::string(who) + ": negative size");
+  MAXK_CHECK_ARG(stats == nullptr || (n_stats >= 1 && n_stats <= 1024),
+                 std::string(who) + ": n_stats must be in [1, 1024]");
+  if (stats_stride == 0) stats_stride = 2;
+  MAXK_CHECK_ARG(stats_stride >= 2 && stats_stride * (int64_t)n_stats < (int64_t)INT32_MAX,
+                 std::string(who) + ": stats_stride must be >= 2 (or 0)");
+  MAXK_CHECK_ARG(D >= 1 && D <= kMaxDim, std::string(who) + ": dim_origin must be in [1, 256]");
+  MAXK_CHECK_ARG(k >= 1 && k <= D, "k must be between 1 and input dimension");
+  if (int rc = check_plan(plan, ptr, idx, N, E, k, D, who)) return rc;
+  const int pl = plan_fwd_layout(plan);
+  if (pl != 1 && pl != 2 && pl != 4) {
+    set_error(std::string(who) + ": the plan's forward gathers the two tables (fwd_layout 0 or "
+                                 "3), it takes no records");
+    return MAXK_ERR_UNSUPPORTED;
+  }
+  if (layout != pl) {
+    set_error(std::string(who) + ": layout is not the plan's fwd_layout");
+    return MAXK_ERR_PLAN_MISMATCH;
+  }
+  if (int rc = check_records(records, record_bytes, layout, k, plan->num_cols > 0, who)) return rc;
+  const bool fixed = plan->fwd_fix && plan->num_cols > 0;
+  MAXK_CHECK_ARG(!fixed || stats,
+                 std::string(who) + ": the plan's forward runs fixed point (maxk_plan_info."
+                                    "fwd_fixed): stats is required (maxk_topk_cbsr_records "
+                                    "writes the pair)");
+  if (N == 0) return MAXK_OK;
+  MAXK_CHECK_ARG(out && ptr && (E == 0 || (idx && val)), std::string(who) + ": null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  // split rows are summed atomically into zeroed rows; no statistics launch zeroes them here
+  const int nz = accumulate ? 0 : plan->n_zero_rows;
+  if (nz > 0) {
+    hipLaunchKernelGGL(zero_rows_kernel, dim3(nz), dim3(256), 0, s, plan->zero_rows, nz, out, D);
+    MAXK_LAUNCH_CHECK("zero_rows launch");
+  }
+  return launch_spgemm_fwd(plan, nullptr, k, nullptr, k, static_cast<const uint8_t*>(records),
+                           (int)record_bytes, nullptr, out, D, k, accumulate,
+                           fixed ? plan->fwd_fix : nullptr, fixed ? stats : nullptr,
+                           fixed ? n_stats : 1, fixed ? (int)stats_stride : 0, fixed ? 1 : 32,
+                           fwd_lds_bytes(plan->fwd_tile_rows, D), s);
 }
 
 extern "C" int maxk_cbsr_stats_tables(const float* sp_data, int64_t data_stride,

@@ -29,6 +29,8 @@ SIGNATURES = {
                                              _i32, _vp]),
     "maxk_topk_cbsr_ex": (ctypes.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i32,
                                          _i32, _i32, _i32, _vp]),
+    "maxk_topk_cbsr_records": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp,
+                                              _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "maxk_topk_stats_scratch_bytes": (ctypes.c_int64, [_i32]),
     "maxk_scatter_backward": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "maxk_scatter_backward_tables": (ctypes.c_int, [_vp, _vp, _i64, _vp, _i32, _i32, _i32, _vp]),
@@ -49,6 +51,8 @@ SIGNATURES = {
     "maxk_spgemm_forward_tables": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp,
                                                   _i32, _i64, _i32, _i32, _i32, _vp, _i32, _i64,
                                                   _vp, _i64, _vp]),
+    "maxk_spgemm_forward_records": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32,
+                                                   _i64, _i32, _i32, _i32, _vp, _i32, _i64, _vp]),
     "maxk_sspmm_backward_tables": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32,
                                                   _i64, _i32, _i32, _vp, _i64, _vp]),
     "maxk_spgemm_forward_ex": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64,
@@ -164,6 +168,7 @@ class PlanInfo(ctypes.Structure):
         # ABI 4
         ("fwd_layout", _i32),
         ("fwd_record_bytes", _i32),
+        ("fwd_fixed", _i32),
     ]
 
     def as_dict(self):

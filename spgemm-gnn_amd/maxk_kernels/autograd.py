@@ -255,23 +255,35 @@ class DenseAggFunction(torch.autograd.Function):
 
 class MaxKAggregateFunction(torch.autograd.Function):
     """``A @ densify(MaxK(x))`` as one producer-consumer pair (utils/maxk_layers.py:16-34:
-    MaxK feeding the SpGEMM). The top-k writes the CBSR features straight into the layout
-    the plan's forward gathers (its packed records when ``fwd_layout`` is 1, GraphPlan.new_cbsr)
-    together with the fixed-point statistics of the emitted rows (maxk_topk_cbsr_ex), so the
-    forward launches no per-call pack or statistics pass. Backward: the SSpMM on the same plan
-    (selectors read at the record stride), then the MaxK scatter (same rules as MaxKFunction
-    for ref_compat padding)."""
+    MaxK feeding the SpGEMM). Where the plan's forward gathers records (``fwd_layout`` 1, 2 or
+    4: every default plan that packs), the top-k writes those records itself
+    (``maxk_topk_cbsr_records``, GraphPlan.new_records) next to a plain ``[N, k]`` selector
+    table for the backward, and the forward gathers them as they are
+    (GraphPlan.forward_records): it launches no per-call pack or statistics pass. Plans that
+    gather the two plain tables (``fwd_layout`` 0 and 3) get plain tables. The fixed-point
+    statistics of the emitted rows come with the top-k only when the forward runs fixed point
+    (``fwd_fixed``), which is the only forward that reads them. Backward: the SSpMM on the same
+    plan, then the MaxK scatter (same rules as MaxKFunction for ref_compat padding)."""
 
     @staticmethod
     def forward(ctx, x: torch.Tensor, graph: CSRGraph, k: int, mode: str = "exact"):
         x = x.contiguous()
         d = x.shape[1]
         plan = graph.plan(d, k)
-        sp_data, sp_index = plan.new_cbsr()
-        stats = torch.empty(2, dtype=torch.int32, device=x.device)
-        res = ops.maxk_forward(x, k, mode=mode, return_index=True, out=(sp_data, sp_index),
-                               stats=stats, return_count=mode != "exact")
-        out = plan.forward(sp_data, sp_index, stats=stats.view(1, 2))
+        stats = torch.empty(2, dtype=torch.int32, device=x.device) if plan.fwd_fixed else None
+        st2 = stats.view(1, 2) if stats is not None else None
+        rec = plan.new_records()
+        if rec is not None:
+            res = ops.maxk_forward(x, k, mode=mode, return_index=True, records=rec,
+                                   return_values=False, stats=stats,
+                                   return_count=mode != "exact")
+            sp_index = res[1]
+            out = plan.forward_records(rec[0], rec[1], stats=st2)
+        else:
+            sp_data, sp_index = plan.new_cbsr()
+            res = ops.maxk_forward(x, k, mode=mode, return_index=True, out=(sp_data, sp_index),
+                                   stats=stats, return_count=mode != "exact")
+            out = plan.forward(sp_data, sp_index, stats=st2)
         ctx.save_for_backward(sp_index, *res[2:])
         ctx.plan = plan
         ctx.dim_origin = d
@@ -318,5 +330,6 @@ def maxk_aggregate(x: torch.Tensor, graph: CSRGraph, k: int, mode: str = "exact"
                    ) -> torch.Tensor:
     """Fused MaxK + aggregation: ``A @ (x * topk_mask(x))`` (DGL: MaxK.apply then
     update_all(u_mul_e, sum) with edge weights ``graph.val``), differentiable in x; the
-    top-k hands the forward its records and statistics (MaxKAggregateFunction)."""
+    top-k writes the records the forward gathers, and the statistics a fixed-point forward
+    needs (MaxKAggregateFunction)."""
     return MaxKAggregateFunction.apply(x, graph, k, mode)

@@ -70,12 +70,25 @@ def _table(t: torch.Tensor, name: str, dtype: torch.dtype, rows: int, k: int) ->
     return t.stride(0) if rows > 1 else k
 
 
+def _records(buf, layout, rows: int, k: int, name: str) -> int:
+    """A u8 [rows, record_bytes] buffer of forward records in chunk layout ``layout`` (1, 2 or
+    4, ``maxk_plan_info.fwd_layout``); rows may be strided: returns the row stride in bytes."""
+    _need(isinstance(buf, torch.Tensor) and buf.is_cuda and buf.dtype == torch.uint8 and
+          buf.dim() == 2 and buf.shape[0] == rows, f"{name} must be a u8 [{rows}, bytes] CUDA tensor")
+    used = {1: 5 * k, 2: 16 * ((k + 2) // 3), 4: 16 * (k // 2)}.get(int(layout), 0)
+    _need(buf.shape[1] >= used, f"{name} rows must hold {used} bytes")
+    _need(rows <= 1 or (buf.stride(1) == 1 and buf.stride(0) >= buf.shape[1]),
+          f"{name} must have unit column stride and row stride >= its width")
+    return buf.stride(0) if rows > 1 else buf.shape[1]
+
+
 # -------------------------------------------------------------------------------------
 # MaxK top-k
 # -------------------------------------------------------------------------------------
 def maxk_forward(input: torch.Tensor, k: int, mode: str = "exact",
                  return_index: bool = False, out=None, return_count: bool = False,
-                 stats: Optional[torch.Tensor] = None):
+                 stats: Optional[torch.Tensor] = None, records=None,
+                 return_values: bool = True):
     """MaxK nonlinearity -> CBSR. Reference: ``maxk_forward(input, k) -> [N, k] f32``.
 
     Checks (bindings.cpp:27-30): "input must be a CUDA tensor", "input must be
@@ -93,6 +106,12 @@ def maxk_forward(input: torch.Tensor, k: int, mode: str = "exact",
     (``maxk_topk_cbsr_ex``; its scratch comes from torch's caching allocator): the pair
     :meth:`GraphPlan.forward` takes as ``stats=stats.view(1, 2)`` instead of its own pass over
     the table.
+    ``records=(buf, layout)``: the top-k also writes each row's forward record into ``buf``,
+    a u8 ``[N, record_bytes]`` CUDA tensor, in the chunk layout ``layout`` (1, 2 or 4:
+    :meth:`GraphPlan.new_records`, ``maxk_topk_cbsr_records``), the table
+    :meth:`GraphPlan.forward_records` gathers as it is. The plain tables are still written and
+    returned; with ``return_values=False`` (records only) the ``[N, k]`` value table is
+    neither allocated nor written and ``None`` stands in its place in the result.
     """
     _need(input.is_cuda, "input must be a CUDA tensor")
     _need(input.is_contiguous(), "input must be contiguous")
@@ -102,8 +121,10 @@ def maxk_forward(input: torch.Tensor, k: int, mode: str = "exact",
     _need(d <= 256, "input dimension must be <= 256 (u8 selectors)")
     _need(input.dtype == torch.float32, "input must be float32")
     _need(mode in TOPK_MODES, f"mode must be one of {sorted(TOPK_MODES)}")
+    _need(return_values or records is not None, "return_values=False needs records")
     if out is None:
-        sp_data = torch.empty((n, k), dtype=torch.float32, device=input.device)
+        sp_data = (torch.empty((n, k), dtype=torch.float32, device=input.device)
+                   if return_values else None)
         sp_index = torch.empty((n, k), dtype=torch.uint8, device=input.device)
         ds = is_ = k
     else:
@@ -121,9 +142,21 @@ def maxk_forward(input: torch.Tensor, k: int, mode: str = "exact",
         sbytes = int(lib.maxk_topk_stats_scratch_bytes(n))
         scratch = torch.empty(sbytes, dtype=torch.uint8, device=input.device)
     with _device(input.device):
-        check(lib.maxk_topk_cbsr_ex(_p(input), _p(sp_data), ds, _p(sp_index), is_, _p(count),
-                                    _p(stats), _p(scratch), sbytes, n, d, k, TOPK_MODES[mode],
-                                    _stream()), "maxk_forward")
+        if records is not None:
+            buf, layout = records
+            rb = _records(buf, layout, n, k, "records")
+            _need(buf.device == input.device, "records must be on the input's device")
+            check(lib.maxk_topk_cbsr_records(_p(input), _p(buf), rb, int(layout),
+                                             _p(sp_data if return_values else None), ds,
+                                             _p(sp_index), is_, _p(count), _p(stats), _p(scratch),
+                                             sbytes, n, d, k, TOPK_MODES[mode], _stream()),
+                  "maxk_forward")
+            if not return_values:
+                sp_data = None
+        else:
+            check(lib.maxk_topk_cbsr_ex(_p(input), _p(sp_data), ds, _p(sp_index), is_, _p(count),
+                                        _p(stats), _p(scratch), sbytes, n, d, k,
+                                        TOPK_MODES[mode], _stream()), "maxk_forward")
     res = (sp_data, sp_index) if return_index else (sp_data,)
     if return_count:
         res = res + (count,)
@@ -257,6 +290,21 @@ class GraphPlan:
                     f"built with options={{'bwd_tp_chunks': P}} (more row chunks) or "
                     f"{{'bwd_algo': 1}} (column blocks) needs less") from exc
 
+    @staticmethod
+    def _stats_arg(stats):
+        """``stats`` of :meth:`forward` as (tensor, pairs, stride in 32-bit words)."""
+        if isinstance(stats, tuple):
+            st, n_st, stride = stats
+            _need(st.is_cuda and st.element_size() == 4 and
+                  (n_st - 1) * stride + 2 <= st.numel(), "stats does not hold n pairs")
+            return st, n_st, stride
+        if stats is not None:
+            _need(stats.is_cuda and stats.is_contiguous() and stats.dtype == torch.int32 and
+                  stats.dim() == 2 and stats.shape[1] == 2 and stats.shape[0] >= 1,
+                  "stats must be a contiguous int32 [n, 2] CUDA tensor")
+            return stats, stats.shape[0], 2
+        return None, 0, 2
+
     def forward(self, sp_data, sp_index, out=None, accumulate: bool = False,
                 stats=None) -> torch.Tensor:
         """SpGEMM with this plan: sp tables [num_cols, k] (rows may be strided, e.g. the
@@ -277,16 +325,7 @@ class GraphPlan:
         stream = torch.cuda.current_stream(self.device)
         self._begin(stream)
         ws, wsb = self._workspace(self.fwd_ws_bytes)
-        st, n_st, stride = None, 0, 2
-        if isinstance(stats, tuple):
-            st, n_st, stride = stats
-            _need(st.is_cuda and st.element_size() == 4 and
-                  (n_st - 1) * stride + 2 <= st.numel(), "stats does not hold n pairs")
-        elif stats is not None:
-            _need(stats.is_cuda and stats.is_contiguous() and stats.dtype == torch.int32 and
-                  stats.dim() == 2 and stats.shape[1] == 2 and stats.shape[0] >= 1,
-                  "stats must be a contiguous int32 [n, 2] CUDA tensor")
-            st, n_st = stats, stats.shape[0]
+        st, n_st, stride = self._stats_arg(stats)
         ds = _table(sp_data, "sp_data", torch.float32, self.num_cols, self.dim_k)
         is_ = _table(sp_index, "sp_index", torch.uint8, self.num_cols, self.dim_k)
         check(lib.maxk_spgemm_forward_tables(self.handle, _p(ptr), _p(idx), _p(val), _p(sp_data),
@@ -295,6 +334,33 @@ class GraphPlan:
                                              int(accumulate), _p(st), n_st, stride, _p(ws), wsb,
                                              ctypes.c_void_p(stream.cuda_stream)),
               "spgemm_forward")
+        self._end(stream)
+        return out
+
+    def forward_records(self, records, layout, out=None, accumulate: bool = False,
+                        stats=None) -> torch.Tensor:
+        """SpGEMM from chunk records the caller holds in this plan's layout (``records`` u8
+        [num_cols, record_bytes] and ``layout`` as :meth:`new_records` returns them, written by
+        :func:`maxk_forward` ``records=``) -> out [num_rows, D]: the forward kernel alone (and
+        the zeroing of split rows), no pack, no statistics pass, no workspace
+        (``maxk_spgemm_forward_records``). ``stats`` as for :meth:`forward`; required when
+        ``info()['fwd_fixed']`` is 1."""
+        ptr, idx, val = self._refs
+        rb = _records(records, layout, self.num_cols, self.dim_k, "records")
+        if out is None:
+            if accumulate:
+                raise RuntimeError("accumulate=True needs an out tensor")
+            out = torch.empty((self.num_rows, self.dim_origin), dtype=torch.float32,
+                              device=records.device)
+        stream = torch.cuda.current_stream(self.device)
+        self._begin(stream)
+        st, n_st, stride = self._stats_arg(stats)
+        check(lib.maxk_spgemm_forward_records(self.handle, _p(ptr), _p(idx), _p(val),
+                                              _p(records), rb, int(layout), _p(out),
+                                              self.num_rows, self.num_edges, self.dim_k,
+                                              self.dim_origin, int(accumulate), _p(st), n_st,
+                                              stride, ctypes.c_void_p(stream.cuda_stream)),
+              "spgemm_forward_records")
         self._end(stream)
         return out
 
@@ -352,16 +418,38 @@ class GraphPlan:
     def device_bytes(self) -> int:
         return int(self.info()["device_bytes"])
 
+    def _fwd_layout(self):
+        """(fwd_layout, fwd_record_bytes, fwd_fixed) of the plan, read once."""
+        layout = getattr(self, "_layout", None)
+        if layout is None:
+            info = self.info()
+            layout = self._layout = (info["fwd_layout"], info["fwd_record_bytes"],
+                                     info["fwd_fixed"])
+        return layout
+
+    @property
+    def fwd_fixed(self) -> bool:
+        """Whether the forward runs fixed point, i.e. consumes the statistics pair."""
+        return bool(self._fwd_layout()[2])
+
+    def new_records(self):
+        """``(records, layout)`` for :func:`maxk_forward` ``records=`` and
+        :meth:`forward_records`: an uninitialised u8 [num_cols, fwd_record_bytes] buffer and the
+        plan's ``fwd_layout`` when that is 1 (packed), 2 (lane chunks) or 4 (pair chunks);
+        ``None`` when the forward gathers the two plain tables (layouts 0 and 3)."""
+        layout, rec_bytes, _ = self._fwd_layout()
+        if layout not in (1, 2, 4):
+            return None
+        return (torch.empty((self.num_cols, rec_bytes), dtype=torch.uint8, device=self.device),
+                layout)
+
     def new_cbsr(self):
         """Uninitialised ``(sp_data, sp_index)`` [num_cols, k] tables in the layout this plan's
         forward gathers (``fwd_layout``): strided views of one buffer of packed records
         (``fwd_record_bytes`` per column, values then selectors) when the forward reads packed
         records, so a top-k written there (:func:`maxk_forward` ``out=``) needs no per-call
         pack; two plain tables otherwise."""
-        layout = getattr(self, "_layout", None)
-        if layout is None:
-            info = self.info()
-            layout = self._layout = (info["fwd_layout"], info["fwd_record_bytes"])
+        layout = self._fwd_layout()
         n, k = self.num_cols, self.dim_k
         if layout[0] == 1 and n > 0:
             rec = torch.empty((n, layout[1]), dtype=torch.uint8, device=self.device)

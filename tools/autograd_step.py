@@ -5,9 +5,14 @@ the host time per step (wall clock of the Python calls without synchronising, i.
 the CPU takes to queue it), and the kernel times of its parts measured alone: top-k, SpGEMM,
 SSpMM, MaxK scatter. Round 6: also the unfused composition (MaxKFunction -> SpGEMMFunction,
 whose forward packs / scans the tables) in the same process, and the fused parts (top-k with
-statistics in the plan's layout, forward given the statistics).
+statistics in the plan's layout, forward given the statistics). Round 7: where the plan's forward
+gathers records (fwd_layout 1, 2, 4) the fused parts are the ones maxk_aggregate runs: the top-k
+writing the records and a plain selector table (statistics only for a fixed-point forward),
+and the forward gathering those records (GraphPlan.forward_records: no pack, no statistics pass).
 
   python tools/autograd_step.py [--dataset reddit] [--k 16]
+  rocprofv3 --kernel-trace --stats ... -- python tools/autograd_step.py --only-step 20
+    (nothing but 20 maxk_aggregate steps: the kernel list of the fused step)
 """
 import argparse
 import json
@@ -50,6 +55,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dataset", default="reddit")
     ap.add_argument("--k", type=int, default=16)
+    ap.add_argument("--only-step", type=int, default=0, metavar="N",
+                    help="run N maxk_aggregate steps and nothing else (for a kernel trace)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     n, _ = graphs.DATASETS[args.dataset]
@@ -74,6 +81,15 @@ def main():
         y = mk.spgemm(sd, si, graph, d)
         y.backward(g)
 
+    if args.only_step:
+        for _ in range(args.only_step):
+            step_fresh()
+        torch.cuda.synchronize()
+        info = graph.plan(d, k).info()
+        print(json.dumps({"dataset": args.dataset, "k": k, "steps": args.only_step,
+                          "fwd_layout": info["fwd_layout"], "fwd_fixed": info["fwd_fixed"],
+                          "fwd_split_rows": info["fwd_split_rows"]}), flush=True)
+        return
     t_step = timeit(step)
     t_fresh = timeit(step_fresh)
     t_unfused = timeit(step_unfused)
@@ -83,14 +99,30 @@ def main():
     sp_data, sp_index = mk.maxk_forward(x.detach(), k, return_index=True)
     out = torch.empty(n, d, device=dev)
     gsp = torch.empty(n, k, device=dev)
-    rd, ri = plan.new_cbsr()
-    st = torch.empty(2, dtype=torch.int32, device=dev)
-    mk.maxk_forward(x.detach(), k, return_index=True, out=(rd, ri), stats=st)
+    fixed = plan.fwd_fixed
+    st = torch.empty(2, dtype=torch.int32, device=dev) if fixed else None
+    st2 = st.view(1, 2) if fixed else None
+    rec = plan.new_records()
+    if rec is not None:
+        def topk_fused():
+            return mk.maxk_forward(x.detach(), k, return_index=True, records=rec,
+                                   return_values=False, stats=st)
+
+        def fwd_fused():
+            return plan.forward_records(rec[0], rec[1], out, stats=st2)
+    else:
+        rd, ri = plan.new_cbsr()
+
+        def topk_fused():
+            return mk.maxk_forward(x.detach(), k, return_index=True, out=(rd, ri), stats=st)
+
+        def fwd_fused():
+            return plan.forward(rd, ri, out, stats=st2)
+    topk_fused()
     fused = {
-        "topk_stats_layout_ms": timeit(lambda: mk.maxk_forward(x.detach(), k, return_index=True,
-                                                                out=(rd, ri), stats=st)),
-        "spgemm_fwd_given_stats_ms": timeit(lambda: plan.forward(rd, ri, out,
-                                                                 stats=st.view(1, 2))),
+        "path": "records" if rec is not None else "tables",
+        "topk_stats_layout_ms": timeit(topk_fused),
+        "spgemm_fwd_given_stats_ms": timeit(fwd_fused),
     }
     parts = {
         "topk_ms": timeit(lambda: mk.maxk_forward(x.detach(), k, return_index=True)),
@@ -99,6 +131,7 @@ def main():
         "maxk_scatter_ms": timeit(lambda: mk.maxk_backward(gsp, sp_index, d)),
     }
     print(json.dumps({"dataset": args.dataset, "k": k, "fwd_layout": plan.info()["fwd_layout"],
+                      "fwd_fixed": int(fixed),
                       "step_ms": t_step, "step_ms_grad_none": t_fresh,
                       "step_ms_grad_none_again": t_fresh2, "step_ms_unfused": t_unfused,
                       "host_ms_per_step": t_host, "fused_parts": fused,
