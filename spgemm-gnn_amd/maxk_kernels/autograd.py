@@ -181,15 +181,17 @@ class MaxKFunction(torch.autograd.Function):
     padding slot never writes (A^T G)[c, 0] into a feature 0 that was not selected."""
 
     @staticmethod
-    def forward(ctx, x: torch.Tensor, k: int, mode: str = "exact"):
+    def forward(ctx, x: torch.Tensor, k: int, mode: str = "exact", dropout=None):
         x = x.contiguous()
         if mode == "exact":
-            sp_data, sp_index = ops.maxk_forward(x, k, mode=mode, return_index=True)
+            sp_data, sp_index = ops.maxk_forward(x, k, mode=mode, return_index=True,
+                                                 dropout=dropout)
             ctx.save_for_backward(sp_index)
         else:
             sp_data, sp_index, count = ops.maxk_forward(x, k, mode=mode, return_index=True,
-                                                        return_count=True)
+                                                        return_count=True, dropout=dropout)
             ctx.save_for_backward(sp_index, count)
+        ctx.dropout = dropout  # (p, seed): the backward recomputes the mask, none is saved
         ctx.dim_origin = x.shape[1]
         ctx.mark_non_differentiable(sp_index)
         return sp_data, sp_index
@@ -201,8 +203,11 @@ class MaxKFunction(torch.autograd.Function):
         grad_data = grad_data.contiguous()
         if len(saved) == 2:
             grad_data, sp_index = _mask_padding(grad_data, sp_index, saved[1])
-        grad_x = ops.maxk_backward(grad_data, sp_index, dim_origin=ctx.dim_origin)
-        return grad_x, None, None
+        # the mask is keyed on the feature, so a padding slot pointed at the last filled slot
+        # gets that slot's mask
+        grad_x = ops.maxk_backward(grad_data, sp_index, dim_origin=ctx.dim_origin,
+                                   dropout=ctx.dropout)
+        return grad_x, None, None, None
 
 
 class SpGEMMFunction(torch.autograd.Function):
@@ -263,10 +268,14 @@ class MaxKAggregateFunction(torch.autograd.Function):
     gather the two plain tables (``fwd_layout`` 0 and 3) get plain tables. The fixed-point
     statistics of the emitted rows come with the top-k only when the forward runs fixed point
     (``fwd_fixed``), which is the only forward that reads them. Backward: the SSpMM on the same
-    plan, then the MaxK scatter (same rules as MaxKFunction for ref_compat padding)."""
+    plan, then the MaxK scatter (same rules as MaxKFunction for ref_compat padding).
+    ``dropout=(p, seed)``: feature dropout between the MaxK and the aggregation, inside the
+    top-k (records and statistics are those of the dropped values, so still no pack and no
+    statistics pass) and inside the scatter; the pair is kept on ``ctx``, no mask tensor."""
 
     @staticmethod
-    def forward(ctx, x: torch.Tensor, graph: CSRGraph, k: int, mode: str = "exact"):
+    def forward(ctx, x: torch.Tensor, graph: CSRGraph, k: int, mode: str = "exact",
+                dropout=None):
         x = x.contiguous()
         d = x.shape[1]
         plan = graph.plan(d, k)
@@ -276,16 +285,17 @@ class MaxKAggregateFunction(torch.autograd.Function):
         if rec is not None:
             res = ops.maxk_forward(x, k, mode=mode, return_index=True, records=rec,
                                    return_values=False, stats=stats,
-                                   return_count=mode != "exact")
+                                   return_count=mode != "exact", dropout=dropout)
             sp_index = res[1]
             out = plan.forward_records(rec[0], rec[1], stats=st2)
         else:
             sp_data, sp_index = plan.new_cbsr()
             res = ops.maxk_forward(x, k, mode=mode, return_index=True, out=(sp_data, sp_index),
-                                   stats=stats, return_count=mode != "exact")
+                                   stats=stats, return_count=mode != "exact", dropout=dropout)
             out = plan.forward(sp_data, sp_index, stats=st2)
         ctx.save_for_backward(sp_index, *res[2:])
         ctx.plan = plan
+        ctx.dropout = dropout
         ctx.dim_origin = d
         return out
 
@@ -298,8 +308,9 @@ class MaxKAggregateFunction(torch.autograd.Function):
             grad_sp = ctx.plan.backward(grad_out.contiguous(), sp_index)
             if len(saved) == 2:
                 grad_sp, sp_index = _mask_padding(grad_sp, sp_index, saved[1])
-            grad_x = ops.maxk_backward(grad_sp, sp_index, dim_origin=ctx.dim_origin)
-        return grad_x, None, None, None
+            grad_x = ops.maxk_backward(grad_sp, sp_index, dim_origin=ctx.dim_origin,
+                                       dropout=ctx.dropout)
+        return grad_x, None, None, None, None
 
 
 def dense_aggregate(x: torch.Tensor, graph: CSRGraph) -> torch.Tensor:
@@ -315,9 +326,26 @@ def densify(sp_data: torch.Tensor, sp_index: torch.Tensor, dim_origin: int) -> t
     return out.scatter_add(1, sp_index.long(), sp_data)
 
 
-def maxk(x: torch.Tensor, k: int, mode: str = "exact"):
-    """(sp_data, sp_index) = MaxK(x), differentiable in x."""
-    return MaxKFunction.apply(x, k, mode)
+def _dropout_pair(dropout_p: float, training: bool, seed):
+    """The ``(p, seed)`` pair of a fused-dropout call, or ``None`` when nothing is dropped.
+    ``seed=None`` draws one int64 from torch's CPU default generator: reproducible under
+    ``torch.manual_seed``, and no device sync."""
+    if not training or dropout_p == 0:
+        return None
+    if not 0.0 <= dropout_p <= 1.0:
+        raise ValueError(f"dropout probability has to be between 0 and 1, but got {dropout_p}")
+    if seed is None:
+        seed = torch.empty((), dtype=torch.int64).random_().item()
+    return float(dropout_p), int(seed)
+
+
+def maxk(x: torch.Tensor, k: int, mode: str = "exact", dropout_p: float = 0.0,
+         training: bool = True, seed: Optional[int] = None):
+    """(sp_data, sp_index) = MaxK(x), differentiable in x. With ``dropout_p > 0`` and
+    ``training``, feature dropout on the kept values inside the top-k kernel (and its scatter in
+    the backward): ``sp_data`` holds ``keep ? x / (1 - p) : 0`` with the counter-based mask of
+    include/maxk_hip.h for ``seed`` (``None``: drawn from torch's CPU generator)."""
+    return MaxKFunction.apply(x, k, mode, _dropout_pair(dropout_p, training, seed))
 
 
 def spgemm(sp_data: torch.Tensor, sp_index: torch.Tensor, graph: CSRGraph,
@@ -327,9 +355,13 @@ def spgemm(sp_data: torch.Tensor, sp_index: torch.Tensor, graph: CSRGraph,
 
 
 def maxk_aggregate(x: torch.Tensor, graph: CSRGraph, k: int, mode: str = "exact",
-                   ) -> torch.Tensor:
+                   dropout_p: float = 0.0, training: bool = True,
+                   seed: Optional[int] = None) -> torch.Tensor:
     """Fused MaxK + aggregation: ``A @ (x * topk_mask(x))`` (DGL: MaxK.apply then
     update_all(u_mul_e, sum) with edge weights ``graph.val``), differentiable in x; the
     top-k writes the records the forward gathers, and the statistics a fixed-point forward
-    needs (MaxKAggregateFunction)."""
-    return MaxKAggregateFunction.apply(x, graph, k, mode)
+    needs (MaxKAggregateFunction). ``dropout_p``, ``training``, ``seed`` as for :func:`maxk`:
+    ``A @ dropout(x * topk_mask(x))`` with the dropout inside the top-k and the scatter, and
+    still no pack or statistics pass."""
+    return MaxKAggregateFunction.apply(x, graph, k, mode,
+                                       _dropout_pair(dropout_p, training, seed))

@@ -31,6 +31,16 @@ utils/models.py:109-411 + dglnn.SAGEConv / GraphConv / GINConv):
   (``maxk_dense_spmm_csr``; backward on the transposed CSR), i.e. the plain DGL layers
   of utils/models.py (``dglnn.SAGEConv(mean)``, ``GraphConv(weight=None)``, ``GINConv``).
 
+``fused_dropout=True`` (every layer and model; default off) moves the ``feat_drop`` of the
+``nonlinear="maxk"`` path into the kernels: in training mode with ``feat_drop > 0`` the
+top-k emits the dropped, scaled values and the MaxK scatter applies the same mask in the
+backward (a counter-based mask of (seed, row, feature), include/maxk_hip.h; one seed per
+layer call from torch's CPU generator), so no ``F.dropout`` pass runs, no mask is saved, and
+GCN and the SAGE ``maxk_after_fc`` branch stay on the fused ``maxk_aggregate`` pair. It is
+the same distribution but other random numbers than ``F.dropout`` draws, which is why it is
+opt-in here; a later change may make it the default. Eval mode and ``feat_drop == 0`` do not
+depend on it.
+
 ``norm`` of ``MaxKSAGEConv`` may be a module instance (DGL's convention) or a class that is
 instantiated as ``norm(out_feats)`` (utils/maxk_layers.py:66-67).
 
@@ -67,6 +77,16 @@ def _sparse_dropout(sp_data: torch.Tensor, p: float, training: bool) -> torch.Te
     return F.dropout(sp_data, p, training) if p > 0 else sp_data
 
 
+def _maxk_dropout(layer, feat: torch.Tensor):
+    """``feat_drop(MaxK(feat))`` as CBSR for a layer: the dropout inside the top-k kernel with
+    ``fused_dropout``, else ``F.dropout`` on the ``[N, k]`` values."""
+    if layer.fused_dropout:
+        return maxk(feat, layer.maxk, layer.topk_mode, dropout_p=layer.feat_drop,
+                    training=layer.training)
+    sp_data, sp_index = maxk(feat, layer.maxk, layer.topk_mode)
+    return _sparse_dropout(sp_data, layer.feat_drop, layer.training), sp_index
+
+
 def _make_norm(norm, out_feats):
     """DGL passes a module instance; the reference layer passes a class and calls
     ``norm(out_feats)`` (utils/maxk_layers.py:66-67). Accept both."""
@@ -86,8 +106,9 @@ class MaxKSAGEConv(nn.Module):
 
     def __init__(self, in_feats, out_feats, aggregator_type="mean", feat_drop=0., norm=None,
                  maxk=32, bias=True, maxk_after_fc=False, topk_mode="exact",
-                 nonlinear="maxk"):
+                 nonlinear="maxk", fused_dropout=False):
         super().__init__()
+        self.fused_dropout = bool(fused_dropout)
         if aggregator_type not in ("mean", "sum"):
             raise ValueError(f"Unsupported aggregator type: {aggregator_type}")
         self.in_feats = in_feats
@@ -120,15 +141,17 @@ class MaxKSAGEConv(nn.Module):
         elif self.maxk_after_fc:
             # reference ordering (maxk_layers.py:85-88): MaxK(fc_neigh(feat)) aggregated
             h_self = self.fc_self(feat)
-            if self.feat_drop > 0 and self.training:
+            if self.feat_drop > 0 and self.training and self.fused_dropout:
+                rst = h_self + maxk_aggregate(self.fc_neigh(feat), csr, self.maxk, self.topk_mode,
+                                              dropout_p=self.feat_drop)
+            elif self.feat_drop > 0 and self.training:
                 sp_data, sp_index = maxk(self.fc_neigh(feat), self.maxk, self.topk_mode)
                 sp_data = _sparse_dropout(sp_data, self.feat_drop, self.training)
                 rst = h_self + spgemm(sp_data, sp_index, csr, self.out_feats)
             else:  # no dropout between MaxK and the SpGEMM: the fused producer-consumer pair
                 rst = h_self + maxk_aggregate(self.fc_neigh(feat), csr, self.maxk, self.topk_mode)
         else:
-            sp_data, sp_index = maxk(feat, self.maxk, self.topk_mode)
-            sp_data = _sparse_dropout(sp_data, self.feat_drop, self.training)
+            sp_data, sp_index = _maxk_dropout(self, feat)
             x = densify(sp_data, sp_index, self.in_feats)
             neigh = spgemm(sp_data, sp_index, csr, self.in_feats)
             rst = self.fc_self(x) + self.fc_neigh(neigh)
@@ -146,8 +169,9 @@ class MaxKGCNConv(nn.Module):
 
     def __init__(self, in_feats, out_feats, norm="both", weight=True, bias=True,
                  allow_zero_in_degree=False, maxk=32, topk_mode="exact", feat_drop=0.,
-                 nonlinear="maxk"):
+                 nonlinear="maxk", fused_dropout=False):
         super().__init__()
+        self.fused_dropout = bool(fused_dropout)
         if norm not in ("both", "right", "left", "none"):
             raise ValueError(f"Invalid norm value {norm!r}")
         self.in_feats = in_feats
@@ -177,6 +201,9 @@ class MaxKGCNConv(nn.Module):
         if self.nonlinear == "relu":
             x = F.dropout(feat, self.feat_drop, self.training) if self.feat_drop > 0 else feat
             rst = dense_aggregate(x, csr.with_values(self.norm))
+        elif self.feat_drop > 0 and self.training and self.fused_dropout:
+            rst = maxk_aggregate(feat, csr.with_values(self.norm), self.maxk, self.topk_mode,
+                                 dropout_p=self.feat_drop)
         elif self.feat_drop > 0 and self.training:
             sp_data, sp_index = maxk(feat, self.maxk, self.topk_mode)
             sp_data = _sparse_dropout(sp_data, self.feat_drop, self.training)
@@ -195,8 +222,9 @@ class MaxKGINConv(nn.Module):
     SpGEMM kernels, or ``x = feat`` and the dense SpMM for ``nonlinear='relu'``."""
 
     def __init__(self, in_feats, out_feats=None, learn_eps=True, maxk=32, init_eps=0.,
-                 topk_mode="exact", feat_drop=0., nonlinear="maxk"):
+                 topk_mode="exact", feat_drop=0., nonlinear="maxk", fused_dropout=False):
         super().__init__()
+        self.fused_dropout = bool(fused_dropout)
         if out_feats is not None and out_feats != in_feats:
             raise ValueError("GINConv without apply_func keeps the feature size")
         self.in_feats = in_feats
@@ -215,8 +243,7 @@ class MaxKGINConv(nn.Module):
         if self.nonlinear == "relu":
             x = F.dropout(feat, self.feat_drop, self.training) if self.feat_drop > 0 else feat
             return (1 + self.eps) * x + dense_aggregate(x, csr)
-        sp_data, sp_index = maxk(feat, self.maxk, self.topk_mode)
-        sp_data = _sparse_dropout(sp_data, self.feat_drop, self.training)
+        sp_data, sp_index = _maxk_dropout(self, feat)
         x = densify(sp_data, sp_index, self.in_feats)
         return (1 + self.eps) * x + spgemm(sp_data, sp_index, csr, self.in_feats)
 
@@ -226,7 +253,7 @@ class MaxKSAGE(nn.Module):
     ``nonlinear='relu'`` the utils/models.py:109-165 SAGE: ReLU, then dglnn.SAGEConv(mean)."""
 
     def __init__(self, in_size, hid_size, num_hid_layers, out_size, maxk=32, feat_drop=0.5,
-                 norm=False, nonlinear="maxk"):
+                 norm=False, nonlinear="maxk", fused_dropout=False):
         super().__init__()
         self.nonlinear = _check_nonlinear(nonlinear)
         self.num_layers = num_hid_layers
@@ -235,7 +262,7 @@ class MaxKSAGE(nn.Module):
         self.layers = nn.ModuleList(
             MaxKSAGEConv(hid_size, hid_size, "mean", feat_drop=feat_drop,
                          norm=nn.LayerNorm(hid_size) if norm else None, maxk=maxk,
-                         nonlinear=nonlinear)
+                         nonlinear=nonlinear, fused_dropout=fused_dropout)
             for _ in range(num_hid_layers))
         nn.init.xavier_uniform_(self.lin_in.weight)
         nn.init.xavier_uniform_(self.lin_out.weight)
@@ -254,7 +281,7 @@ class MaxKGCN(nn.Module):
     -> LayerNorm)."""
 
     def __init__(self, in_size, hid_size, num_hid_layers, out_size, maxk=32, feat_drop=0.5,
-                 norm=False, nonlinear="maxk"):
+                 norm=False, nonlinear="maxk", fused_dropout=False):
         super().__init__()
         self.nonlinear = _check_nonlinear(nonlinear)
         self.num_layers = num_hid_layers
@@ -264,7 +291,8 @@ class MaxKGCN(nn.Module):
                                        for _ in range(num_hid_layers))
         self.gcnlayers = nn.ModuleList(MaxKGCNConv(hid_size, hid_size, weight=False, maxk=maxk,
                                                    allow_zero_in_degree=True,
-                                                   feat_drop=feat_drop, nonlinear=nonlinear)
+                                                   feat_drop=feat_drop, nonlinear=nonlinear,
+                                                   fused_dropout=fused_dropout)
                                        for _ in range(num_hid_layers))
         self.normlayers = nn.ModuleList(nn.LayerNorm(hid_size) for _ in range(num_hid_layers)
                                         ) if norm else None
@@ -288,7 +316,7 @@ class MaxKGIN(nn.Module):
     -> LayerNorm), the constructor of utils/integrated_models.py:145-149."""
 
     def __init__(self, in_size, hid_size, num_hid_layers, out_size, maxk=32, feat_drop=0.5,
-                 norm=False, nonlinear="maxk"):
+                 norm=False, nonlinear="maxk", fused_dropout=False):
         super().__init__()
         self.nonlinear = _check_nonlinear(nonlinear)
         self.num_layers = num_hid_layers
@@ -297,7 +325,8 @@ class MaxKGIN(nn.Module):
         self.linlayers = nn.ModuleList(nn.Linear(hid_size, hid_size)
                                        for _ in range(num_hid_layers))
         self.ginlayers = nn.ModuleList(MaxKGINConv(hid_size, maxk=maxk, feat_drop=feat_drop,
-                                                   nonlinear=nonlinear)
+                                                   nonlinear=nonlinear,
+                                                   fused_dropout=fused_dropout)
                                        for _ in range(num_hid_layers))
         self.normlayers = nn.ModuleList(nn.LayerNorm(hid_size) for _ in range(num_hid_layers)
                                         ) if norm else None

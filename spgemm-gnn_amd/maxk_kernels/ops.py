@@ -82,13 +82,28 @@ def _records(buf, layout, rows: int, k: int, name: str) -> int:
     return buf.stride(0) if rows > 1 else buf.shape[1]
 
 
+def _dropout_arg(dropout):
+    """``dropout`` of :func:`maxk_forward` / :func:`maxk_backward` as ``(p, seed, row_offset)``
+    with the seed taken modulo 2^64, or ``None`` when there is nothing to drop (``None`` or
+    ``p == 0``: the path without dropout, unchanged)."""
+    if dropout is None:
+        return None
+    _need(isinstance(dropout, (tuple, list)) and len(dropout) in (2, 3),
+          "dropout must be (p, seed) or (p, seed, row_offset)")
+    p, seed = float(dropout[0]), int(dropout[1]) & 0xFFFFFFFFFFFFFFFF
+    row_offset = int(dropout[2]) if len(dropout) == 3 else 0
+    if p == 0.0 and row_offset >= 0:
+        return None
+    return p, seed, row_offset
+
+
 # -------------------------------------------------------------------------------------
 # MaxK top-k
 # -------------------------------------------------------------------------------------
 def maxk_forward(input: torch.Tensor, k: int, mode: str = "exact",
                  return_index: bool = False, out=None, return_count: bool = False,
                  stats: Optional[torch.Tensor] = None, records=None,
-                 return_values: bool = True):
+                 return_values: bool = True, dropout=None):
     """MaxK nonlinearity -> CBSR. Reference: ``maxk_forward(input, k) -> [N, k] f32``.
 
     Checks (bindings.cpp:27-30): "input must be a CUDA tensor", "input must be
@@ -112,6 +127,11 @@ def maxk_forward(input: torch.Tensor, k: int, mode: str = "exact",
     :meth:`GraphPlan.forward_records` gathers as it is. The plain tables are still written and
     returned; with ``return_values=False`` (records only) the ``[N, k]`` value table is
     neither allocated nor written and ``None`` stands in its place in the result.
+    ``dropout=(p, seed)`` or ``(p, seed, row_offset)``: feature dropout fused into the top-k
+    (``maxk_topk_cbsr_dropout``): the emitted values, in tables, records and statistics alike,
+    are ``keep ? x / (1 - p) : +0.0`` with the counter-based mask of include/maxk_hip.h keyed on
+    ``(seed, row_offset + row, feature)``; selectors and counts are those of the undropped
+    input. ``seed`` is any int, taken modulo 2^64. ``None`` or ``p == 0`` is today's path.
     """
     _need(input.is_cuda, "input must be a CUDA tensor")
     _need(input.is_contiguous(), "input must be contiguous")
@@ -141,8 +161,22 @@ def maxk_forward(input: torch.Tensor, k: int, mode: str = "exact",
               "stats must be a contiguous int32 CUDA tensor of 2 elements on the input's device")
         sbytes = int(lib.maxk_topk_stats_scratch_bytes(n))
         scratch = torch.empty(sbytes, dtype=torch.uint8, device=input.device)
+    drop = _dropout_arg(dropout)
     with _device(input.device):
-        if records is not None:
+        if drop is not None:
+            buf, layout, rb = None, 0, 0
+            if records is not None:
+                buf, layout = records
+                rb = _records(buf, layout, n, k, "records")
+                _need(buf.device == input.device, "records must be on the input's device")
+            check(lib.maxk_topk_cbsr_dropout(_p(input), _p(buf), rb, int(layout),
+                                             _p(sp_data if return_values else None), ds,
+                                             _p(sp_index), is_, _p(count), _p(stats), _p(scratch),
+                                             sbytes, n, d, k, TOPK_MODES[mode], drop[0], drop[1],
+                                             drop[2], _stream()), "maxk_forward")
+            if not return_values:
+                sp_data = None
+        elif records is not None:
             buf, layout = records
             rb = _records(buf, layout, n, k, "records")
             _need(buf.device == input.device, "records must be on the input's device")
@@ -164,7 +198,7 @@ def maxk_forward(input: torch.Tensor, k: int, mode: str = "exact",
 
 
 def maxk_backward(grad_output: torch.Tensor, indices: torch.Tensor,
-                  dim_origin: Optional[int] = None) -> torch.Tensor:
+                  dim_origin: Optional[int] = None, dropout=None) -> torch.Tensor:
     """Dense gradient of MaxK from the ``[N, k]`` CBSR gradient.
 
     Reference (maxk_backward_cuda SO@0x21410): ``g = zeros(N, max(indices)+1)``;
@@ -172,6 +206,9 @@ def maxk_backward(grad_output: torch.Tensor, indices: torch.Tensor,
     grad_output CUDA/contiguous/2-D, indices CUDA/contiguous. Here one device kernel does
     the scatter; pass ``dim_origin`` for a stable ``[N, dim_origin]`` shape (without it the
     reference's data-dependent width ``max(indices)+1`` is kept, which costs a host sync).
+    ``dropout`` as for :func:`maxk_forward` (``maxk_scatter_backward_dropout``): each loaded
+    value becomes ``keep(row, selector) ? g / (1 - p) : +0.0``, the backward of the top-k
+    called with the same tuple.
     """
     _need(grad_output.is_cuda, "grad_output must be a CUDA tensor")
     _need(grad_output.is_contiguous(), "grad_output must be contiguous")
@@ -193,10 +230,17 @@ def maxk_backward(grad_output: torch.Tensor, indices: torch.Tensor,
         dim_origin = int(indices.max().item()) + 1 if indices.numel() else 1
     _need(1 <= k <= dim_origin <= 256, "k must be between 1 and input dimension")
     grad_in = torch.empty((n, dim_origin), dtype=torch.float32, device=grad_output.device)
+    drop = _dropout_arg(dropout)
     with _device(grad_output.device):
-        check(lib.maxk_scatter_backward_tables(_p(grad_output), _p(indices), istride,
-                                               _p(grad_in), n, dim_origin, k, _stream()),
-              "maxk_backward")
+        if drop is not None:
+            check(lib.maxk_scatter_backward_dropout(_p(grad_output), _p(indices), istride,
+                                                    _p(grad_in), n, dim_origin, k, drop[0],
+                                                    drop[1], drop[2], _stream()),
+                  "maxk_backward")
+        else:
+            check(lib.maxk_scatter_backward_tables(_p(grad_output), _p(indices), istride,
+                                                   _p(grad_in), n, dim_origin, k, _stream()),
+                  "maxk_backward")
     return grad_in
 
 

@@ -14,6 +14,10 @@ formula (the SSpMM backward) as a registered derivative.
     torch.ops.maxk.spgemm_backward(ptr, idx, val, grad_output, sp_index, num_nodes,
                                    num_edges, dim_k, dim_origin) -> grad_sp [num_nodes, dim_k]
 
+    torch.ops.maxk.maxk_dropout_forward(input, k, p, seed) -> (sp_data, sp_index)
+    torch.ops.maxk.maxk_dropout_backward(grad_output, indices, dim_origin, p, seed)
+                                  -> [N, dim_origin]   (MaxK with fused feature dropout)
+
 The real kernels are :mod:`maxk_kernels.ops` (the HIP C ABI); there is no other
 implementation behind these names. Differences from the plain functions, all forced by
 the operator schema: ``maxk_forward`` always returns the selectors (the reference drops
@@ -113,3 +117,49 @@ def _maxk_backward(ctx, grad_data, grad_index):
 
 
 maxk_forward.register_autograd(_maxk_backward, setup_context=_maxk_setup)
+
+
+# MaxK with fused feature dropout (ops.maxk_forward / ops.maxk_backward ``dropout=``). ``seed``
+# is an int64 schema int, reinterpreted as the uint64 seed of the mask.
+@torch.library.custom_op(f"{_NS}::maxk_dropout_forward", mutates_args=())
+def maxk_dropout_forward(input: torch.Tensor, k: int, p: float,
+                         seed: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """MaxK top-k -> CBSR with dropout on the kept values (exact mode)."""
+    return ops.maxk_forward(input, k, return_index=True, dropout=(p, seed))
+
+
+@maxk_dropout_forward.register_fake
+def _(input, k, p, seed):
+    n = input.shape[0]
+    return (input.new_empty((n, k)), input.new_empty((n, k), dtype=torch.uint8))
+
+
+@torch.library.custom_op(f"{_NS}::maxk_dropout_backward", mutates_args=())
+def maxk_dropout_backward(grad_output: torch.Tensor, indices: torch.Tensor, dim_origin: int,
+                          p: float, seed: int) -> torch.Tensor:
+    """Dense MaxK gradient through the same dropout mask (ops.maxk_backward ``dropout=``)."""
+    return ops.maxk_backward(grad_output, indices, dim_origin, dropout=(p, seed))
+
+
+@maxk_dropout_backward.register_fake
+def _(grad_output, indices, dim_origin, p, seed):
+    return grad_output.new_empty((grad_output.shape[0], dim_origin))
+
+
+def _maxk_dropout_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[1])
+    ctx.dim_origin = inputs[0].shape[1]
+    ctx.dropout = (inputs[2], inputs[3])
+
+
+def _maxk_dropout_backward(ctx, grad_data, grad_index):
+    (sp_index,) = ctx.saved_tensors
+    if grad_data is None:
+        return None, None, None, None
+    return (torch.ops.maxk.maxk_dropout_backward(grad_data.contiguous(), sp_index,
+                                                 ctx.dim_origin, *ctx.dropout),
+            None, None, None)
+
+
+maxk_dropout_forward.register_autograd(_maxk_dropout_backward,
+                                       setup_context=_maxk_dropout_setup)

@@ -10,7 +10,13 @@ gathers records (fwd_layout 1, 2, 4) the fused parts are the ones maxk_aggregate
 writing the records and a plain selector table (statistics only for a fixed-point forward),
 and the forward gathering those records (GraphPlan.forward_records: no pack, no statistics pass).
 
-  python tools/autograd_step.py [--dataset reddit] [--k 16]
+Round 8: --dropout P times the step with feature dropout fused into the top-k and the scatter
+(maxk_aggregate(..., dropout_p=P)) against the composition a layer with feat_drop ran before
+(maxk -> F.dropout -> spgemm, same graph and k) in the same process, the composition twice
+(before and after the fused step) so its own spread is known, with each step's peak memory
+above the resident tensors, and the dropout top-k / scatter kernels next to the plain ones.
+
+  python tools/autograd_step.py [--dataset reddit] [--k 16] [--dropout 0.5]
   rocprofv3 --kernel-trace --stats ... -- python tools/autograd_step.py --only-step 20
     (nothing but 20 maxk_aggregate steps: the kernel list of the fused step)
 """
@@ -51,12 +57,72 @@ def host_time(fn, reps=20):
     return (t1 - t0) * 1e3 / reps
 
 
+def peak_bytes(fn):
+    """Peak device memory of one call above what is resident before it."""
+    fn()
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    fn()
+    torch.cuda.synchronize()
+    return torch.cuda.max_memory_allocated() - base
+
+
+def dropout_report(args, graph, x, g, d, k, step_dropout, step_composed):
+    p, dev, n = args.dropout, x.device, x.shape[0]
+    t_comp1 = timeit(step_composed)
+    t_fused = timeit(step_dropout)
+    t_comp2 = timeit(step_composed)
+    t_fused2 = timeit(step_dropout)
+    mem_fused, mem_comp = peak_bytes(step_dropout), peak_bytes(step_composed)
+    plan = graph.plan(d, k)
+    fixed = plan.fwd_fixed
+    st = torch.empty(2, dtype=torch.int32, device=dev) if fixed else None
+    rec = plan.new_records()
+    xd = x.detach()
+    if rec is not None:
+        def topk(drop):
+            return mk.maxk_forward(xd, k, return_index=True, records=rec, return_values=False,
+                                   stats=st, dropout=drop)
+    else:
+        out = plan.new_cbsr()
+
+        def topk(drop):
+            return mk.maxk_forward(xd, k, return_index=True, out=out, stats=st, dropout=drop)
+    sp_index = topk(None)[1]
+    gsp = graphs.features(n, k, seed=99, device=dev)
+    seed = 0x9E3779B97F4A7C15
+    kern = {
+        "topk_ms": timeit(lambda: topk(None)),
+        "topk_dropout_ms": timeit(lambda: topk((p, seed))),
+        "topk_tables_ms": timeit(lambda: mk.maxk_forward(xd, k, return_index=True)),
+        "topk_tables_dropout_ms": timeit(lambda: mk.maxk_forward(xd, k, return_index=True,
+                                                                 dropout=(p, seed))),
+        "scatter_ms": timeit(lambda: mk.maxk_backward(gsp, sp_index, d)),
+        "scatter_dropout_ms": timeit(lambda: mk.maxk_backward(gsp, sp_index, d,
+                                                              dropout=(p, seed))),
+    }
+    kern["topk_ratio"] = kern["topk_dropout_ms"] / kern["topk_ms"]
+    kern["topk_tables_ratio"] = kern["topk_tables_dropout_ms"] / kern["topk_tables_ms"]
+    kern["scatter_ratio"] = kern["scatter_dropout_ms"] / kern["scatter_ms"]
+    info = plan.info()
+    print(json.dumps({"dataset": args.dataset, "k": k, "dropout": p,
+                      "fwd_layout": info["fwd_layout"], "fwd_fixed": int(fixed),
+                      "step_ms_fused_dropout": t_fused, "step_ms_fused_dropout_again": t_fused2,
+                      "step_ms_composed": [t_comp1, t_comp2],
+                      "fused_not_slower": t_fused <= max(t_comp1, t_comp2),
+                      "peak_bytes_fused": mem_fused, "peak_bytes_composed": mem_comp,
+                      "peak_bytes_saved": mem_comp - mem_fused, "kernels": kern}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dataset", default="reddit")
     ap.add_argument("--k", type=int, default=16)
     ap.add_argument("--only-step", type=int, default=0, metavar="N",
                     help="run N maxk_aggregate steps and nothing else (for a kernel trace)")
+    ap.add_argument("--dropout", type=float, default=0.0, metavar="P",
+                    help="time the fused-dropout step against maxk -> F.dropout -> spgemm")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     n, _ = graphs.DATASETS[args.dataset]
@@ -81,14 +147,32 @@ def main():
         y = mk.spgemm(sd, si, graph, d)
         y.backward(g)
 
+    p_drop = args.dropout
+
+    def step_dropout():  # dropout inside the top-k and the scatter: seed drawn per step
+        x.grad = None
+        y = mk.maxk_aggregate(x, graph, k, dropout_p=p_drop)
+        y.backward(g)
+
+    def step_composed():  # what a layer with feat_drop > 0 ran before: a mask tensor, a
+        x.grad = None     # dropped [N, k] copy, and the forward's pack / statistics pass
+        sd, si = mk.maxk(x, k)
+        sd = torch.nn.functional.dropout(sd, p_drop, True)
+        y = mk.spgemm(sd, si, graph, d)
+        y.backward(g)
+
     if args.only_step:
         for _ in range(args.only_step):
-            step_fresh()
+            step_dropout() if p_drop > 0 else step_fresh()
         torch.cuda.synchronize()
         info = graph.plan(d, k).info()
         print(json.dumps({"dataset": args.dataset, "k": k, "steps": args.only_step,
+                          "dropout": p_drop,
                           "fwd_layout": info["fwd_layout"], "fwd_fixed": info["fwd_fixed"],
                           "fwd_split_rows": info["fwd_split_rows"]}), flush=True)
+        return
+    if p_drop > 0:
+        dropout_report(args, graph, x, g, d, k, step_dropout, step_composed)
         return
     t_step = timeit(step)
     t_fresh = timeit(step_fresh)
