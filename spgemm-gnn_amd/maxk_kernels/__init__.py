@@ -32,11 +32,13 @@ from .autograd import (  # noqa: F401
     DenseAggFunction,
     MaxKAggregateFunction,
     MaxKFunction,
+    MaxKSelfAggregateFunction,
     SpGEMMFunction,
     dense_aggregate,
     densify,
     maxk,
     maxk_aggregate,
+    maxk_self_aggregate,
     spgemm,
 )
 
@@ -55,7 +57,8 @@ __all__ = [
     "dense_spmm", "cbsr_stats", "plan_col_order", "GraphPlan", "get_plan", "clear_plan_cache", "CSRGraph",
     "MaxKFunction", "MaxKAggregateFunction", "SpGEMMFunction", "maxk", "spgemm", "maxk_aggregate", "MaxKError",
     "densify", "MaxKSAGEConv", "MaxKGCNConv", "MaxKGINConv", "MaxKSAGE", "MaxKGCN",
-    "MaxKGIN", "dense_aggregate", "DenseAggFunction",
+    "MaxKGIN", "dense_aggregate", "DenseAggFunction", "MaxKSelfAggregateFunction",
+    "maxk_self_aggregate",
 ]
 
 ABI_VERSION = lib.maxk_abi_version()

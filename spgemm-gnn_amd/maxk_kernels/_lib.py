@@ -36,6 +36,11 @@ SIGNATURES = {
                                               ctypes.c_uint64, _i64, _vp]),
     "maxk_scatter_backward_dropout": (ctypes.c_int, [_vp, _vp, _i64, _vp, _i32, _i32, _i32,
                                                      ctypes.c_float, ctypes.c_uint64, _i64, _vp]),
+    "maxk_topk_cbsr_dense": (ctypes.c_int, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _i64,
+                                            _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32,
+                                            ctypes.c_float, ctypes.c_uint64, _i64, _vp]),
+    "maxk_scatter_backward_merge": (ctypes.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32,
+                                                   ctypes.c_float, ctypes.c_uint64, _i64, _vp]),
     "maxk_topk_stats_scratch_bytes": (ctypes.c_int64, [_i32]),
     "maxk_scatter_backward": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "maxk_scatter_backward_tables": (ctypes.c_int, [_vp, _vp, _i64, _vp, _i32, _i32, _i32, _vp]),

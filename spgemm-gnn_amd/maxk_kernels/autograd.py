@@ -313,6 +313,75 @@ class MaxKAggregateFunction(torch.autograd.Function):
         return grad_x, None, None, None, None
 
 
+class MaxKSelfAggregateFunction(torch.autograd.Function):
+    """``(x_m, A @ x_m)`` with ``x_m = dropout(x * topk_mask(x))`` dense ``[N, D]``: the pair a
+    layer with a self term needs (``fc_self(x_m)`` in GraphSAGE, ``(1 + eps) x_m`` in GIN) from
+    one top-k launch. Forward as :class:`MaxKAggregateFunction` (records, or plain tables for
+    plans that gather those; the statistics pair only for a fixed-point forward), with the
+    top-k also storing the dense masked row from the registers that hold it
+    (``maxk_topk_cbsr_dense``): no ``densify`` fill and scatter, no pack, no statistics pass.
+    Only the selectors are saved (and the slot counts in ref_compat mode). Backward: the SSpMM
+    when the aggregated output has a gradient, then one scatter that adds the dense output's
+    gradient at the selected features before the dropout factor
+    (``maxk_scatter_backward_merge``): no gather of ``densify``'s gradient, no ``[N, k]`` add."""
+
+    @staticmethod
+    def forward(ctx, x: torch.Tensor, graph: CSRGraph, k: int, mode: str = "exact",
+                dropout=None):
+        x = x.contiguous()
+        d = x.shape[1]
+        plan = graph.plan(d, k)
+        stats = torch.empty(2, dtype=torch.int32, device=x.device) if plan.fwd_fixed else None
+        st2 = stats.view(1, 2) if stats is not None else None
+        x_m = torch.empty_like(x)
+        rec = plan.new_records()
+        if rec is not None:
+            res = ops.maxk_forward(x, k, mode=mode, return_index=True, records=rec,
+                                   return_values=False, stats=stats,
+                                   return_count=mode != "exact", dropout=dropout, dense=x_m)
+            sp_index = res[1]
+            out = plan.forward_records(rec[0], rec[1], stats=st2)
+        else:
+            sp_data, sp_index = plan.new_cbsr()
+            res = ops.maxk_forward(x, k, mode=mode, return_index=True, out=(sp_data, sp_index),
+                                   stats=stats, return_count=mode != "exact", dropout=dropout,
+                                   dense=x_m)
+            out = plan.forward(sp_data, sp_index, stats=st2)
+        ctx.save_for_backward(sp_index, *res[2:])
+        ctx.plan = plan
+        ctx.dropout = dropout
+        ctx.dim_origin = d
+        ctx.set_materialize_grads(False)  # an unused output arrives as None, not as zeros
+        return x_m, out
+
+    @staticmethod
+    def backward(ctx, g_self, g_agg):
+        saved = ctx.saved_tensors
+        sp_index = saved[0]
+        if not ctx.needs_input_grad[0] or (g_self is None and g_agg is None):
+            return None, None, None, None, None
+        grad_sp = None
+        if g_agg is not None:
+            grad_sp = ctx.plan.backward(g_agg.contiguous(), sp_index)
+        if len(saved) == 2:
+            # a padding slot repeats the last filled slot's selector and gradient, so the last
+            # slot still wins with the same sum
+            if grad_sp is None:
+                grad_sp = torch.zeros(sp_index.shape, dtype=torch.float32,
+                                      device=sp_index.device)
+            grad_sp, sp_index = _mask_padding(grad_sp, sp_index, saved[1])
+        if g_self is not None and (g_self.stride(1) != 1 or g_self.stride(0) < ctx.dim_origin):
+            g_self = g_self.contiguous()
+        grad_x = ops.maxk_backward(grad_sp, sp_index, dim_origin=ctx.dim_origin,
+                                   dropout=ctx.dropout, grad_dense=g_self)
+        if len(saved) == 2 and g_self is not None:
+            # a row that fills no slot (a constant row) has no last filled slot to point at:
+            # its slots stay (selector 0, gradient 0), which is harmless without g_self, but
+            # the merge would add g_self[r, 0] into a feature 0 that was not selected
+            grad_x.masked_fill_((saved[1] == 0)[:, None], 0.0)
+        return grad_x, None, None, None, None
+
+
 def dense_aggregate(x: torch.Tensor, graph: CSRGraph) -> torch.Tensor:
     """Y = A @ x for dense x (ReLU layers), differentiable in x."""
     return DenseAggFunction.apply(x, graph)
@@ -365,3 +434,16 @@ def maxk_aggregate(x: torch.Tensor, graph: CSRGraph, k: int, mode: str = "exact"
     still no pack or statistics pass."""
     return MaxKAggregateFunction.apply(x, graph, k, mode,
                                        _dropout_pair(dropout_p, training, seed))
+
+
+def maxk_self_aggregate(x: torch.Tensor, graph: CSRGraph, k: int, mode: str = "exact",
+                        dropout_p: float = 0.0, training: bool = True,
+                        seed: Optional[int] = None):
+    """``(x_masked [N, D], agg [N, D])``: ``x_masked = dropout(x * topk_mask(x))`` dense and
+    ``agg = A @ x_masked``, both differentiable in x (MaxKSelfAggregateFunction): what
+    ``maxk`` → ``densify`` → ``spgemm`` computes, from one top-k launch that writes the dense
+    row, the forward's records and their statistics, and with one scatter in the backward that
+    merges both outputs' gradients. ``agg`` is :func:`maxk_aggregate` of the same arguments,
+    bit for bit. ``dropout_p``, ``training``, ``seed`` as for :func:`maxk`."""
+    return MaxKSelfAggregateFunction.apply(x, graph, k, mode,
+                                           _dropout_pair(dropout_p, training, seed))

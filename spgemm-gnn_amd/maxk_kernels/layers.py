@@ -41,6 +41,15 @@ the same distribution but other random numbers than ``F.dropout`` draws, which i
 opt-in here; a later change may make it the default. Eval mode and ``feat_drop == 0`` do not
 depend on it.
 
+Layers with a self term (``MaxKSAGEConv`` in its default ordering, ``MaxKGINConv``) need
+``x = feat_drop(MaxK(feat))`` twice, aggregated and dense. Whenever no ``F.dropout`` has to sit
+between MaxK and the aggregation (``feat_drop == 0``, eval mode, or ``fused_dropout=True``)
+they take both from ``maxk_self_aggregate``: the top-k writes the dense masked row next to the
+forward's records, and one scatter merges both gradients in the backward (no ``densify``, no
+per-call pack or statistics pass, no ``[N, k]`` value table saved). Training with
+``feat_drop > 0`` and ``fused_dropout=False`` keeps the composition ``maxk`` → ``F.dropout`` →
+``densify`` / ``spgemm``, because it draws ``F.dropout``'s random numbers.
+
 ``norm`` of ``MaxKSAGEConv`` may be a module instance (DGL's convention) or a class that is
 instantiated as ``norm(out_feats)`` (utils/maxk_layers.py:66-67).
 
@@ -53,7 +62,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .autograd import CSRGraph, dense_aggregate, densify, maxk, maxk_aggregate, spgemm
+from .autograd import (CSRGraph, dense_aggregate, densify, maxk, maxk_aggregate,
+                       maxk_self_aggregate, spgemm)
 
 NONLINEAR = ("maxk", "relu")
 
@@ -85,6 +95,18 @@ def _maxk_dropout(layer, feat: torch.Tensor):
                     training=layer.training)
     sp_data, sp_index = maxk(feat, layer.maxk, layer.topk_mode)
     return _sparse_dropout(sp_data, layer.feat_drop, layer.training), sp_index
+
+
+def _maxk_self_pair(layer, feat: torch.Tensor, csr: CSRGraph):
+    """``(x, A @ x)`` with ``x = feat_drop(MaxK(feat))`` dense, for a layer with a self term:
+    ``maxk_self_aggregate`` unless ``F.dropout`` has to sit between MaxK and the aggregation
+    (training with ``feat_drop > 0`` and no ``fused_dropout``)."""
+    if layer.feat_drop > 0 and layer.training and not layer.fused_dropout:
+        sp_data, sp_index = _maxk_dropout(layer, feat)
+        return (densify(sp_data, sp_index, layer.in_feats),
+                spgemm(sp_data, sp_index, csr, layer.in_feats))
+    return maxk_self_aggregate(feat, csr, layer.maxk, layer.topk_mode,
+                               dropout_p=layer.feat_drop, training=layer.training)
 
 
 def _make_norm(norm, out_feats):
@@ -151,9 +173,7 @@ class MaxKSAGEConv(nn.Module):
             else:  # no dropout between MaxK and the SpGEMM: the fused producer-consumer pair
                 rst = h_self + maxk_aggregate(self.fc_neigh(feat), csr, self.maxk, self.topk_mode)
         else:
-            sp_data, sp_index = _maxk_dropout(self, feat)
-            x = densify(sp_data, sp_index, self.in_feats)
-            neigh = spgemm(sp_data, sp_index, csr, self.in_feats)
+            x, neigh = _maxk_self_pair(self, feat, csr)
             rst = self.fc_self(x) + self.fc_neigh(neigh)
         if self.bias is not None:
             rst = rst + self.bias
@@ -243,9 +263,8 @@ class MaxKGINConv(nn.Module):
         if self.nonlinear == "relu":
             x = F.dropout(feat, self.feat_drop, self.training) if self.feat_drop > 0 else feat
             return (1 + self.eps) * x + dense_aggregate(x, csr)
-        sp_data, sp_index = _maxk_dropout(self, feat)
-        x = densify(sp_data, sp_index, self.in_feats)
-        return (1 + self.eps) * x + spgemm(sp_data, sp_index, csr, self.in_feats)
+        x, neigh = _maxk_self_pair(self, feat, csr)
+        return (1 + self.eps) * x + neigh
 
 
 class MaxKSAGE(nn.Module):

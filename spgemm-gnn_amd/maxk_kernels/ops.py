@@ -103,7 +103,7 @@ def _dropout_arg(dropout):
 def maxk_forward(input: torch.Tensor, k: int, mode: str = "exact",
                  return_index: bool = False, out=None, return_count: bool = False,
                  stats: Optional[torch.Tensor] = None, records=None,
-                 return_values: bool = True, dropout=None):
+                 return_values: bool = True, dropout=None, dense=None):
     """MaxK nonlinearity -> CBSR. Reference: ``maxk_forward(input, k) -> [N, k] f32``.
 
     Checks (bindings.cpp:27-30): "input must be a CUDA tensor", "input must be
@@ -132,6 +132,12 @@ def maxk_forward(input: torch.Tensor, k: int, mode: str = "exact",
     are ``keep ? x / (1 - p) : +0.0`` with the counter-based mask of include/maxk_hip.h keyed on
     ``(seed, row_offset + row, feature)``; selectors and counts are those of the undropped
     input. ``seed`` is any int, taken modulo 2^64. ``None`` or ``p == 0`` is today's path.
+    ``dense``: an f32 ``[N, D]`` tensor on the input's device, contiguous or row-strided (unit
+    column stride, row stride >= D), that receives the dense masked row with the same launch
+    (``maxk_topk_cbsr_dense``): ``dense[r, f]`` is the value the table holds for the filled
+    slot that selected ``f`` (dropped and scaled under ``dropout``), ``+0.0`` for every other
+    feature. It must not overlap ``input``. The return value is unchanged; with ``dense`` given,
+    ``return_values=False`` needs no ``records``.
     """
     _need(input.is_cuda, "input must be a CUDA tensor")
     _need(input.is_contiguous(), "input must be contiguous")
@@ -141,7 +147,14 @@ def maxk_forward(input: torch.Tensor, k: int, mode: str = "exact",
     _need(d <= 256, "input dimension must be <= 256 (u8 selectors)")
     _need(input.dtype == torch.float32, "input must be float32")
     _need(mode in TOPK_MODES, f"mode must be one of {sorted(TOPK_MODES)}")
-    _need(return_values or records is not None, "return_values=False needs records")
+    _need(return_values or records is not None or dense is not None,
+          "return_values=False needs records")
+    dstride = 0
+    if dense is not None:
+        _need(isinstance(dense, torch.Tensor) and dense.is_cuda and dense.device == input.device,
+              "dense must be a CUDA tensor on the input's device")
+        _need(dense.dtype == torch.float32, "dense must be float32")
+        dstride = _table(dense, "dense", torch.float32, n, d)
     if out is None:
         sp_data = (torch.empty((n, k), dtype=torch.float32, device=input.device)
                    if return_values else None)
@@ -163,7 +176,21 @@ def maxk_forward(input: torch.Tensor, k: int, mode: str = "exact",
         scratch = torch.empty(sbytes, dtype=torch.uint8, device=input.device)
     drop = _dropout_arg(dropout)
     with _device(input.device):
-        if drop is not None:
+        if dense is not None:
+            buf, layout, rb = None, 0, 0
+            if records is not None:
+                buf, layout = records
+                rb = _records(buf, layout, n, k, "records")
+                _need(buf.device == input.device, "records must be on the input's device")
+            p, seed, row_offset = drop if drop is not None else (0.0, 0, 0)
+            check(lib.maxk_topk_cbsr_dense(_p(input), _p(dense), dstride, _p(buf), rb, int(layout),
+                                           _p(sp_data if return_values else None), ds,
+                                           _p(sp_index), is_, _p(count), _p(stats), _p(scratch),
+                                           sbytes, n, d, k, TOPK_MODES[mode], p, seed, row_offset,
+                                           _stream()), "maxk_forward")
+            if not return_values:
+                sp_data = None
+        elif drop is not None:
             buf, layout, rb = None, 0, 0
             if records is not None:
                 buf, layout = records
@@ -197,8 +224,9 @@ def maxk_forward(input: torch.Tensor, k: int, mode: str = "exact",
     return res if len(res) > 1 else res[0]
 
 
-def maxk_backward(grad_output: torch.Tensor, indices: torch.Tensor,
-                  dim_origin: Optional[int] = None, dropout=None) -> torch.Tensor:
+def maxk_backward(grad_output: Optional[torch.Tensor], indices: torch.Tensor,
+                  dim_origin: Optional[int] = None, dropout=None,
+                  grad_dense: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Dense gradient of MaxK from the ``[N, k]`` CBSR gradient.
 
     Reference (maxk_backward_cuda SO@0x21410): ``g = zeros(N, max(indices)+1)``;
@@ -209,14 +237,26 @@ def maxk_backward(grad_output: torch.Tensor, indices: torch.Tensor,
     ``dropout`` as for :func:`maxk_forward` (``maxk_scatter_backward_dropout``): each loaded
     value becomes ``keep(row, selector) ? g / (1 - p) : +0.0``, the backward of the top-k
     called with the same tuple.
+    ``grad_dense``: the f32 ``[N, dim_origin]`` gradient of the dense masked row
+    (:func:`maxk_forward` ``dense=``; rows may be strided), added at the selected features
+    before the dropout factor (``maxk_scatter_backward_merge``):
+    ``keep ? (grad_dense[r, f] + grad_output[r, j]) / (1 - p) : +0.0``; features no slot selects
+    stay 0 whatever ``grad_dense`` holds there. With it ``grad_output`` may be ``None`` (only
+    the dense output was used); the shape then comes from ``indices`` and ``dim_origin``.
     """
-    _need(grad_output.is_cuda, "grad_output must be a CUDA tensor")
-    _need(grad_output.is_contiguous(), "grad_output must be contiguous")
-    _need(grad_output.dim() == 2, "grad_output must be 2D tensor")
     _need(indices.is_cuda, "indices must be a CUDA tensor")
-    _need(indices.shape == grad_output.shape, "indices must have the shape of grad_output")
-    _need(grad_output.dtype == torch.float32, "grad_output must be float32")
-    n, k = grad_output.shape
+    if grad_output is None:
+        _need(grad_dense is not None, "grad_output=None needs grad_dense")
+        _need(indices.dim() == 2, "indices must be 2D tensor")
+        device = indices.device
+    else:
+        _need(grad_output.is_cuda, "grad_output must be a CUDA tensor")
+        _need(grad_output.is_contiguous(), "grad_output must be contiguous")
+        _need(grad_output.dim() == 2, "grad_output must be 2D tensor")
+        _need(indices.shape == grad_output.shape, "indices must have the shape of grad_output")
+        _need(grad_output.dtype == torch.float32, "grad_output must be float32")
+        device = grad_output.device
+    n, k = indices.shape
     # u8 selectors may be row-strided (the interleaved records of maxk_aggregate); other
     # integer dtypes are converted (contiguous)
     strided_u8 = (indices.dtype == torch.uint8 and indices.dim() == 2 and
@@ -229,10 +269,19 @@ def maxk_backward(grad_output: torch.Tensor, indices: torch.Tensor,
     if dim_origin is None:
         dim_origin = int(indices.max().item()) + 1 if indices.numel() else 1
     _need(1 <= k <= dim_origin <= 256, "k must be between 1 and input dimension")
-    grad_in = torch.empty((n, dim_origin), dtype=torch.float32, device=grad_output.device)
+    grad_in = torch.empty((n, dim_origin), dtype=torch.float32, device=device)
     drop = _dropout_arg(dropout)
-    with _device(grad_output.device):
-        if drop is not None:
+    with _device(device):
+        if grad_dense is not None:
+            _need(isinstance(grad_dense, torch.Tensor) and grad_dense.is_cuda and
+                  grad_dense.device == device, "grad_dense must be a CUDA tensor on the same device")
+            gstride = _table(grad_dense, "grad_dense", torch.float32, n, dim_origin)
+            p, seed, row_offset = drop if drop is not None else (0.0, 0, 0)
+            check(lib.maxk_scatter_backward_merge(_p(grad_output), _p(indices), istride,
+                                                  _p(grad_dense), gstride, _p(grad_in), n,
+                                                  dim_origin, k, p, seed, row_offset, _stream()),
+                  "maxk_backward")
+        elif drop is not None:
             check(lib.maxk_scatter_backward_dropout(_p(grad_output), _p(indices), istride,
                                                     _p(grad_in), n, dim_origin, k, drop[0],
                                                     drop[1], drop[2], _stream()),

@@ -18,6 +18,11 @@ formula (the SSpMM backward) as a registered derivative.
     torch.ops.maxk.maxk_dropout_backward(grad_output, indices, dim_origin, p, seed)
                                   -> [N, dim_origin]   (MaxK with fused feature dropout)
 
+    torch.ops.maxk.maxk_dense_forward(input, k, p, seed) -> (dense [N, D], sp_data, sp_index)
+    torch.ops.maxk.maxk_merge_backward(grad_output (or None), indices, grad_dense, p, seed)
+                                  -> [N, D]   (MaxK that also emits the dense masked row; the
+                                     scatter adds the dense row's gradient; p = 0: no dropout)
+
 The real kernels are :mod:`maxk_kernels.ops` (the HIP C ABI); there is no other
 implementation behind these names. Differences from the plain functions, all forced by
 the operator schema: ``maxk_forward`` always returns the selectors (the reference drops
@@ -27,7 +32,7 @@ them); ``maxk_backward`` takes ``dim_origin`` (a data-dependent width has no fak
 """
 from __future__ import annotations
 
-from typing import Tuple
+from typing import Optional, Tuple
 
 import torch
 
@@ -163,3 +168,61 @@ def _maxk_dropout_backward(ctx, grad_data, grad_index):
 
 maxk_dropout_forward.register_autograd(_maxk_dropout_backward,
                                        setup_context=_maxk_dropout_setup)
+
+
+# MaxK that also emits the dense masked row (ops.maxk_forward ``dense=``) and the scatter that
+# merges the two outputs' gradients (ops.maxk_backward ``grad_dense=``); ``p == 0``: no dropout.
+@torch.library.custom_op(f"{_NS}::maxk_dense_forward", mutates_args=())
+def maxk_dense_forward(input: torch.Tensor, k: int, p: float,
+                       seed: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """MaxK top-k -> (dense masked row, CBSR values, selectors), exact mode."""
+    dense = torch.empty_like(input, memory_format=torch.contiguous_format)
+    sp_data, sp_index = ops.maxk_forward(input, k, return_index=True, dropout=(p, seed),
+                                         dense=dense)
+    return dense, sp_data, sp_index
+
+
+@maxk_dense_forward.register_fake
+def _(input, k, p, seed):
+    n = input.shape[0]
+    return (input.new_empty(input.shape), input.new_empty((n, k)),
+            input.new_empty((n, k), dtype=torch.uint8))
+
+
+@torch.library.custom_op(f"{_NS}::maxk_merge_backward", mutates_args=())
+def maxk_merge_backward(grad_output: Optional[torch.Tensor], indices: torch.Tensor,
+                        grad_dense: torch.Tensor, p: float, seed: int) -> torch.Tensor:
+    """Dense MaxK gradient of both outputs of ``maxk_dense_forward`` (the width is
+    ``grad_dense``'s); ``grad_output=None``: only the dense output was used."""
+    return ops.maxk_backward(grad_output, indices, grad_dense.shape[1], dropout=(p, seed),
+                             grad_dense=grad_dense)
+
+
+@maxk_merge_backward.register_fake
+def _(grad_output, indices, grad_dense, p, seed):
+    return grad_dense.new_empty(grad_dense.shape)
+
+
+def _maxk_dense_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[2])
+    ctx.shape = tuple(inputs[0].shape)
+    ctx.dropout = (inputs[2], inputs[3])
+    ctx.set_materialize_grads(False)  # an unused output arrives as None, not as zeros
+
+
+def _maxk_dense_backward(ctx, grad_dense, grad_data, grad_index):
+    (sp_index,) = ctx.saved_tensors
+    if grad_dense is None and grad_data is None:
+        return None, None, None, None
+    if grad_dense is None:
+        return (torch.ops.maxk.maxk_dropout_backward(grad_data.contiguous(), sp_index,
+                                                     ctx.shape[1], *ctx.dropout),
+                None, None, None)
+    if grad_data is not None:
+        grad_data = grad_data.contiguous()
+    return (torch.ops.maxk.maxk_merge_backward(grad_data, sp_index, grad_dense.contiguous(),
+                                               *ctx.dropout),
+            None, None, None)
+
+
+maxk_dense_forward.register_autograd(_maxk_dense_backward, setup_context=_maxk_dense_setup)

@@ -16,7 +16,13 @@ Round 8: --dropout P times the step with feature dropout fused into the top-k an
 (before and after the fused step) so its own spread is known, with each step's peak memory
 above the resident tensors, and the dropout top-k / scatter kernels next to the plain ones.
 
-  python tools/autograd_step.py [--dataset reddit] [--k 16] [--dropout 0.5]
+Round 9: --self times the step of a layer with a self term (GraphSAGE, GIN):
+x_m, y = maxk_self_aggregate(x, graph, k), backward with upstream gradients for both outputs,
+against the composition maxk -> densify -> spgemm (with F.dropout on the [N, k] values under
+--dropout) in the same process, the composition before and after the fused step, each step's
+peak memory, and the dense top-k / merge scatter kernels next to the plain ones.
+
+  python tools/autograd_step.py [--dataset reddit] [--k 16] [--dropout 0.5] [--self]
   rocprofv3 --kernel-trace --stats ... -- python tools/autograd_step.py --only-step 20
     (nothing but 20 maxk_aggregate steps: the kernel list of the fused step)
 """
@@ -115,6 +121,59 @@ def dropout_report(args, graph, x, g, d, k, step_dropout, step_composed):
                       "peak_bytes_saved": mem_comp - mem_fused, "kernels": kern}), flush=True)
 
 
+def self_report(args, graph, x, g, g_self, d, k, step_self, step_self_composed):
+    p, dev, n = args.dropout, x.device, x.shape[0]
+    t_comp1 = timeit(step_self_composed)
+    t_fused = timeit(step_self)
+    t_comp2 = timeit(step_self_composed)
+    t_fused2 = timeit(step_self)
+    mem_fused, mem_comp = peak_bytes(step_self), peak_bytes(step_self_composed)
+    plan = graph.plan(d, k)
+    fixed = plan.fwd_fixed
+    st = torch.empty(2, dtype=torch.int32, device=dev) if fixed else None
+    rec = plan.new_records()
+    xd = x.detach()
+    dense = torch.empty_like(xd)
+    seed = 0x9E3779B97F4A7C15
+    drop = (p, seed) if p > 0 else None
+    if rec is not None:
+        def topk(dn):
+            return mk.maxk_forward(xd, k, return_index=True, records=rec, return_values=False,
+                                   stats=st, dropout=drop, dense=dn)
+    else:
+        out = plan.new_cbsr()
+
+        def topk(dn):
+            return mk.maxk_forward(xd, k, return_index=True, out=out, stats=st, dropout=drop,
+                                   dense=dn)
+    sp_index = topk(None)[1]
+    sp_data = mk.maxk_forward(xd, k, dropout=drop)
+    gsp = graphs.features(n, k, seed=99, device=dev)
+    idx64 = sp_index.long()
+    kern = {
+        "topk_ms": timeit(lambda: topk(None)),
+        "topk_dense_ms": timeit(lambda: topk(dense)),
+        "scatter_ms": timeit(lambda: mk.maxk_backward(gsp, sp_index, d, dropout=drop)),
+        "scatter_merge_ms": timeit(lambda: mk.maxk_backward(gsp, sp_index, d, dropout=drop,
+                                                            grad_dense=g_self)),
+        # the passes of the composition that the two kernels replace
+        "densify_ms": timeit(lambda: mk.densify(sp_data, sp_index, d)),
+        "densify_grad_gather_add_ms": timeit(lambda: g_self.gather(1, idx64) + gsp),
+        "index_long_ms": timeit(lambda: sp_index.long()),
+    }
+    info = plan.info()
+    slower = max(t_comp1, t_comp2)
+    print(json.dumps({"dataset": args.dataset, "k": k, "self": True, "dropout": p,
+                      "fwd_layout": info["fwd_layout"], "fwd_fixed": int(fixed),
+                      "step_ms_self_fused": t_fused, "step_ms_self_fused_again": t_fused2,
+                      "step_ms_self_composed": [t_comp1, t_comp2],
+                      "fused_not_slower": t_fused <= slower,
+                      "speedup_vs_slower_composed": slower / t_fused,
+                      "speedup_vs_faster_composed": min(t_comp1, t_comp2) / t_fused,
+                      "peak_bytes_fused": mem_fused, "peak_bytes_composed": mem_comp,
+                      "peak_bytes_saved": mem_comp - mem_fused, "kernels": kern}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dataset", default="reddit")
@@ -123,6 +182,9 @@ def main():
                     help="run N maxk_aggregate steps and nothing else (for a kernel trace)")
     ap.add_argument("--dropout", type=float, default=0.0, metavar="P",
                     help="time the fused-dropout step against maxk -> F.dropout -> spgemm")
+    ap.add_argument("--self", dest="self_term", action="store_true",
+                    help="time maxk_self_aggregate (dense masked row + aggregation) against "
+                         "maxk -> densify -> spgemm")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     n, _ = graphs.DATASETS[args.dataset]
@@ -161,15 +223,37 @@ def main():
         y = mk.spgemm(sd, si, graph, d)
         y.backward(g)
 
+    g_self = graphs.features(n, d, seed=96, device=dev) if args.self_term else None
+
+    def step_self():  # a layer with a self term: the dense masked row and its aggregation
+        x.grad = None
+        xm, y = mk.maxk_self_aggregate(x, graph, k, dropout_p=p_drop)
+        torch.autograd.backward([xm, y], [g_self, g])
+
+    def step_self_composed():  # what those layers ran before
+        x.grad = None
+        sd, si = mk.maxk(x, k)
+        if p_drop > 0:
+            sd = torch.nn.functional.dropout(sd, p_drop, True)
+        xm = mk.densify(sd, si, d)
+        y = mk.spgemm(sd, si, graph, d)
+        torch.autograd.backward([xm, y], [g_self, g])
+
     if args.only_step:
         for _ in range(args.only_step):
-            step_dropout() if p_drop > 0 else step_fresh()
+            if args.self_term:
+                step_self()
+            else:
+                step_dropout() if p_drop > 0 else step_fresh()
         torch.cuda.synchronize()
         info = graph.plan(d, k).info()
         print(json.dumps({"dataset": args.dataset, "k": k, "steps": args.only_step,
-                          "dropout": p_drop,
+                          "dropout": p_drop, "self": args.self_term,
                           "fwd_layout": info["fwd_layout"], "fwd_fixed": info["fwd_fixed"],
                           "fwd_split_rows": info["fwd_split_rows"]}), flush=True)
+        return
+    if args.self_term:
+        self_report(args, graph, x, g, g_self, d, k, step_self, step_self_composed)
         return
     if p_drop > 0:
         dropout_report(args, graph, x, g, d, k, step_dropout, step_composed)
