@@ -98,6 +98,12 @@ void set_error(const std::string& msg);
     }                                                                           \
   } while (0)
 
+// Whether [a, a + na) and [b, b + nb) (bytes) share a byte.
+inline bool ranges_overlap(const void* a, int64_t na, const void* b, int64_t nb) {
+  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+  return na > 0 && nb > 0 && x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
+}
+
 // Forward work item: a run of whole destination rows [row0, row0+nrows) (or, nrows < 0, one
 // segment of a long row whose partial sum is added atomically into a row pre-zeroed by
 // zero_rows), with edge range [e0, e1) of the plan's permuted edge order (the task's CSR

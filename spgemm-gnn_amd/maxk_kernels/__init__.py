@@ -25,11 +25,14 @@ from .ops import (  # noqa: F401
     maxk_forward,
     plan_col_order,
     spgemm_backward,
+    spgemm_edge_grad,
     spgemm_forward,
 )
 from .autograd import (  # noqa: F401
     CSRGraph,
     DenseAggFunction,
+    DenseEdgeWeightedFunction,
+    EdgeWeightedFunction,
     MaxKAggregateFunction,
     MaxKFunction,
     MaxKSelfAggregateFunction,
@@ -58,7 +61,7 @@ __all__ = [
     "MaxKFunction", "MaxKAggregateFunction", "SpGEMMFunction", "maxk", "spgemm", "maxk_aggregate", "MaxKError",
     "densify", "MaxKSAGEConv", "MaxKGCNConv", "MaxKGINConv", "MaxKSAGE", "MaxKGCN",
     "MaxKGIN", "dense_aggregate", "DenseAggFunction", "MaxKSelfAggregateFunction",
-    "maxk_self_aggregate",
+    "maxk_self_aggregate", "spgemm_edge_grad", "EdgeWeightedFunction", "DenseEdgeWeightedFunction",
 ]
 
 ABI_VERSION = lib.maxk_abi_version()

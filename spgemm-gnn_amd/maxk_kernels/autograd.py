@@ -11,6 +11,10 @@ module that does not exist) and its ``MaxKFunction`` (utils/maxk_layers.py:16-45
 * :class:`SpGEMMFunction` maps CBSR features to ``Y = A @ densify(sp)`` (SpGEMM forward)
   and back-propagates with the SSpMM kernel, ``grad_sp = (A^T G)`` sampled at the
   selector.
+* :class:`EdgeWeightedFunction` is the aggregation with the edge values as a differentiable
+  input (``edge_weight=`` on :func:`spgemm`, :func:`maxk_aggregate`,
+  :func:`maxk_self_aggregate`): the same kernels on a value-refreshed plan, plus the SDDMM
+  ``ops.spgemm_edge_grad`` for the values' gradient.
 """
 from __future__ import annotations
 
@@ -59,6 +63,18 @@ class CSRGraph:
     def plan(self, dim_origin: int, dim_k: int) -> ops.GraphPlan:
         return ops.get_plan(self.ptr, self.idx, self.val, self.num_nodes, self.num_edges,
                             dim_origin, dim_k)
+
+    def weighted_plan(self, dim_origin: int, dim_k: int) -> ops.GraphPlan:
+        """The plan for edge values that change from call to call (``edge_weight=``): cached on
+        this graph per (D, k), apart from :meth:`plan`, built once and from then on only
+        value-refreshed (``GraphPlan.refresh_values``) to each call's effective values."""
+        key = ("weighted_plan", int(dim_origin), int(dim_k))
+        plan = self._values.get(key)
+        if plan is None:
+            plan = ops.GraphPlan(self.ptr, self.idx, self.val, self.num_nodes, self.num_edges,
+                                 int(dim_origin), int(dim_k))
+            self._values[key] = plan
+        return plan
 
     # -- construction -----------------------------------------------------------------
     @classmethod
@@ -145,6 +161,21 @@ class CSRGraph:
                             if not (isinstance(k, tuple) and k[0] == "transposed")}
             self._values[key] = g
         return g
+
+    def transposed_structure(self):
+        """``(ptr_t, idx_t, order)`` of A^T, cached: edge j of A^T is edge ``order[j]`` of A,
+        so changing values are transposed by one gather and no sort."""
+        st = self._values.get("transposed_structure")
+        if st is None:
+            rows = torch.repeat_interleave(torch.arange(self.num_nodes, device=self.device),
+                                           self.in_degrees())
+            cols = self.idx.to(torch.int64)
+            order = torch.argsort(cols * self.num_nodes + rows, stable=True)
+            ptr = torch.zeros(self.num_nodes + 1, dtype=torch.int64, device=self.device)
+            ptr[1:] = torch.cumsum(torch.bincount(cols, minlength=self.num_nodes), 0)
+            st = (ptr.to(torch.int32), rows[order].to(torch.int32).contiguous(), order)
+            self._values["transposed_structure"] = st
+        return st
 
     def with_values(self, kind: str) -> "CSRGraph":
         """Same structure with the ``kind`` edge weights (shares ptr/idx, hence the plan)."""
@@ -382,8 +413,145 @@ class MaxKSelfAggregateFunction(torch.autograd.Function):
         return grad_x, None, None, None, None
 
 
-def dense_aggregate(x: torch.Tensor, graph: CSRGraph) -> torch.Tensor:
-    """Y = A @ x for dense x (ReLU layers), differentiable in x."""
+class EdgeWeightedFunction(torch.autograd.Function):
+    """The aggregation with the edge values as an explicit differentiable input ``val [E]`` (the
+    effective values ``graph.val * edge_weight``), for the three entry points that take
+    ``edge_weight=``. ``form``:
+
+    * ``"spgemm"``: ``feat`` is ``sp_data`` (with ``sp_index`` and ``dim_origin``) -> ``out``;
+    * ``"aggregate"``: ``feat`` is dense ``x`` -> ``out``, as :class:`MaxKAggregateFunction`;
+    * ``"self"``: ``feat`` is dense ``x`` -> ``(x_m, out)``, as :class:`MaxKSelfAggregateFunction`.
+
+    Forward: the kernels of those Functions on ``graph.weighted_plan``, value-refreshed to
+    ``val``. The plain ``[N, k]`` value table of the fused forms is emitted and saved only when
+    ``val`` needs a gradient. Backward: the SSpMM and the scatter as there, plus
+    ``ops.spgemm_edge_grad`` for ``val`` when asked. The plan's value snapshot is shared by
+    every weighted call on the graph, so the backward re-refreshes it when another call's values
+    are in it; ``val`` is kept on ``ctx`` for that."""
+
+    @staticmethod
+    def forward(ctx, feat, val, graph, form, sp_index, dim_origin, k, mode, dropout):
+        feat, val = feat.contiguous(), val.contiguous()
+        need_val = ctx.needs_input_grad[1]
+        d = dim_origin if form == "spgemm" else feat.shape[1]
+        k = feat.shape[1] if form == "spgemm" else k
+        plan = graph.weighted_plan(d, k)
+        plan.refresh_values(val)
+        x_m, extra = None, ()
+        if form == "spgemm":
+            sp_data = feat
+            out, _ = ops.spgemm_forward(graph.ptr, graph.idx, val, sp_data, sp_index,
+                                        graph.num_nodes, graph.num_edges, k, d, plan=plan)
+        else:
+            stats = torch.empty(2, dtype=torch.int32, device=feat.device) if plan.fwd_fixed else None
+            st2 = stats.view(1, 2) if stats is not None else None
+            x_m = torch.empty_like(feat) if form == "self" else None
+            rec = plan.new_records()
+            if rec is not None:
+                res = ops.maxk_forward(feat, k, mode=mode, return_index=True, records=rec,
+                                       return_values=need_val, stats=stats,
+                                       return_count=mode != "exact", dropout=dropout, dense=x_m)
+                out = plan.forward_records(rec[0], rec[1], stats=st2)
+            else:
+                res = ops.maxk_forward(feat, k, mode=mode, return_index=True, out=plan.new_cbsr(),
+                                       stats=stats, return_count=mode != "exact",
+                                       dropout=dropout, dense=x_m)
+                out = plan.forward(res[0], res[1], stats=st2)
+            sp_data, sp_index, extra = res[0], res[1], res[2:]
+        ctx.save_for_backward(sp_index, *extra, *((sp_data,) if need_val else ()))
+        ctx.has_count, ctx.has_data = len(extra) == 1, need_val
+        ctx.graph, ctx.plan, ctx.val = graph, plan, val
+        ctx.form, ctx.dropout, ctx.dims = form, dropout, (d, k)
+        ctx.set_materialize_grads(False)  # an unused output arrives as None, not as zeros
+        return (x_m, out) if form == "self" else out
+
+    @staticmethod
+    def backward(ctx, *grads):
+        none = (None,) * 7
+        g_agg = grads[-1]
+        g_self = grads[0] if ctx.form == "self" else None
+        saved = ctx.saved_tensors
+        sp_index = saved[0]
+        count = saved[1] if ctx.has_count else None
+        graph, plan, val = ctx.graph, ctx.plan, ctx.val
+        d, k = ctx.dims
+        grad_val = grad_feat = None
+        if g_agg is not None:
+            g_agg = g_agg.contiguous()
+            if ctx.needs_input_grad[1]:
+                grad_val = ops.spgemm_edge_grad(graph.ptr, graph.idx, g_agg, saved[-1], sp_index,
+                                                graph.num_nodes, graph.num_edges, k, d)
+        if ctx.needs_input_grad[0] and (g_agg is not None or g_self is not None):
+            grad_sp = None
+            if g_agg is not None:
+                if plan._refs[2] is not val or plan.val_version != val._version:
+                    plan.refresh_values(val)  # another weighted call ran on this graph since
+                grad_sp = plan.backward(g_agg, sp_index)
+            if ctx.form == "spgemm":
+                return (grad_sp, grad_val) + none
+            # from here on as MaxKSelfAggregateFunction.backward (g_self None: the scatter of
+            # MaxKAggregateFunction)
+            if count is not None:
+                if grad_sp is None:
+                    grad_sp = torch.zeros(sp_index.shape, dtype=torch.float32,
+                                          device=sp_index.device)
+                grad_sp, sp_index = _mask_padding(grad_sp, sp_index, count)
+            if g_self is not None and (g_self.stride(1) != 1 or g_self.stride(0) < d):
+                g_self = g_self.contiguous()
+            grad_feat = ops.maxk_backward(grad_sp, sp_index, dim_origin=d, dropout=ctx.dropout,
+                                          grad_dense=g_self)
+            if count is not None and g_self is not None:
+                grad_feat.masked_fill_((count == 0)[:, None], 0.0)
+        return (grad_feat, grad_val) + none
+
+
+class DenseEdgeWeightedFunction(torch.autograd.Function):
+    """:class:`DenseAggFunction` with the edge values as a differentiable input ``val [E]``:
+    ``Y = A(val) X`` (the ReLU layers with ``edge_weight=``). Backward: ``dX = A(val)^T dY`` by
+    the same SpMM on the cached transposed structure (the values are gathered, not re-sorted),
+    and ``d val`` by ``ops.spgemm_edge_grad`` run with ``k = D`` on ``X`` itself as the value
+    table and identity selectors (so D % 4 == 0 and D <= 256 when ``val`` needs a gradient)."""
+
+    @staticmethod
+    def forward(ctx, x, val, graph):
+        x, val = x.contiguous(), val.contiguous()
+        ctx.graph = graph
+        ctx.save_for_backward(val, *((x,) if ctx.needs_input_grad[1] else ()))
+        return ops.dense_spmm(graph.ptr, graph.idx, val, x)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        val, graph = ctx.saved_tensors[0], ctx.graph
+        grad_out = grad_out.contiguous()
+        grad_x = grad_val = None
+        if ctx.needs_input_grad[0]:
+            ptr_t, idx_t, order = graph.transposed_structure()
+            grad_x = ops.dense_spmm(ptr_t, idx_t, val[order], grad_out)
+        if ctx.needs_input_grad[1]:
+            x = ctx.saved_tensors[1]
+            n, d = x.shape
+            ident = torch.arange(d, dtype=torch.uint8, device=x.device).repeat(n, 1)
+            grad_val = ops.spgemm_edge_grad(graph.ptr, graph.idx, grad_out, x, ident, n,
+                                            graph.num_edges, d, d)
+        return grad_x, grad_val, None
+
+
+def _effective_values(graph: CSRGraph, edge_weight: torch.Tensor) -> torch.Tensor:
+    """``graph.val * edge_weight`` (a torch multiply: the chain rule to ``edge_weight`` is
+    torch's); ``edge_weight`` is f32 ``[E]`` on the graph's device, in the CSRGraph's edge order."""
+    if not (isinstance(edge_weight, torch.Tensor) and edge_weight.dtype == torch.float32 and
+            edge_weight.shape == (graph.num_edges,) and edge_weight.device == graph.device):
+        raise RuntimeError("edge_weight must be a float32 [num_edges] tensor on the graph's "
+                           "device, in the CSRGraph's edge order")
+    return graph.val * edge_weight
+
+
+def dense_aggregate(x: torch.Tensor, graph: CSRGraph,
+                    edge_weight: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Y = A @ x for dense x (ReLU layers), differentiable in x, and in ``edge_weight`` (the
+    edge values are then ``graph.val * edge_weight``) when one is given."""
+    if edge_weight is not None:
+        return DenseEdgeWeightedFunction.apply(x, _effective_values(graph, edge_weight), graph)
     return DenseAggFunction.apply(x, graph)
 
 
@@ -418,32 +586,49 @@ def maxk(x: torch.Tensor, k: int, mode: str = "exact", dropout_p: float = 0.0,
 
 
 def spgemm(sp_data: torch.Tensor, sp_index: torch.Tensor, graph: CSRGraph,
-           dim_origin: int) -> torch.Tensor:
-    """Y = A @ densify(sp_data, sp_index), differentiable in sp_data."""
+           dim_origin: int, edge_weight: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Y = A @ densify(sp_data, sp_index), differentiable in sp_data. ``edge_weight``: f32
+    ``[E]`` on the graph's device, in the CSRGraph's own edge order; the edge values are then
+    ``graph.val * edge_weight`` and Y is differentiable in ``edge_weight`` too (DGL's
+    ``u_mul_e``; EdgeWeightedFunction). ``None`` is the path without it, unchanged."""
+    if edge_weight is not None:
+        return EdgeWeightedFunction.apply(sp_data, _effective_values(graph, edge_weight), graph,
+                                          "spgemm", sp_index, dim_origin, None, None, None)
     return SpGEMMFunction.apply(sp_data, sp_index, graph, dim_origin)
 
 
 def maxk_aggregate(x: torch.Tensor, graph: CSRGraph, k: int, mode: str = "exact",
                    dropout_p: float = 0.0, training: bool = True,
-                   seed: Optional[int] = None) -> torch.Tensor:
+                   seed: Optional[int] = None,
+                   edge_weight: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Fused MaxK + aggregation: ``A @ (x * topk_mask(x))`` (DGL: MaxK.apply then
     update_all(u_mul_e, sum) with edge weights ``graph.val``), differentiable in x; the
     top-k writes the records the forward gathers, and the statistics a fixed-point forward
     needs (MaxKAggregateFunction). ``dropout_p``, ``training``, ``seed`` as for :func:`maxk`:
     ``A @ dropout(x * topk_mask(x))`` with the dropout inside the top-k and the scatter, and
-    still no pack or statistics pass."""
+    still no pack or statistics pass. ``edge_weight`` as for :func:`spgemm`."""
+    if edge_weight is not None:
+        return EdgeWeightedFunction.apply(x, _effective_values(graph, edge_weight), graph,
+                                          "aggregate", None, None, k, mode,
+                                          _dropout_pair(dropout_p, training, seed))
     return MaxKAggregateFunction.apply(x, graph, k, mode,
                                        _dropout_pair(dropout_p, training, seed))
 
 
 def maxk_self_aggregate(x: torch.Tensor, graph: CSRGraph, k: int, mode: str = "exact",
                         dropout_p: float = 0.0, training: bool = True,
-                        seed: Optional[int] = None):
+                        seed: Optional[int] = None,
+                        edge_weight: Optional[torch.Tensor] = None):
     """``(x_masked [N, D], agg [N, D])``: ``x_masked = dropout(x * topk_mask(x))`` dense and
     ``agg = A @ x_masked``, both differentiable in x (MaxKSelfAggregateFunction): what
     ``maxk`` → ``densify`` → ``spgemm`` computes, from one top-k launch that writes the dense
     row, the forward's records and their statistics, and with one scatter in the backward that
     merges both outputs' gradients. ``agg`` is :func:`maxk_aggregate` of the same arguments,
-    bit for bit. ``dropout_p``, ``training``, ``seed`` as for :func:`maxk`."""
+    bit for bit. ``dropout_p``, ``training``, ``seed`` as for :func:`maxk`; ``edge_weight`` as
+    for :func:`spgemm` (it weights ``agg`` only)."""
+    if edge_weight is not None:
+        return EdgeWeightedFunction.apply(x, _effective_values(graph, edge_weight), graph, "self",
+                                          None, None, k, mode,
+                                          _dropout_pair(dropout_p, training, seed))
     return MaxKSelfAggregateFunction.apply(x, graph, k, mode,
                                            _dropout_pair(dropout_p, training, seed))

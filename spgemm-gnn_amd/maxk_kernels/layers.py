@@ -55,6 +55,14 @@ instantiated as ``norm(out_feats)`` (utils/maxk_layers.py:66-67).
 
 ``graph`` may be a :class:`~maxk_kernels.autograd.CSRGraph` or a DGL graph (converted
 with ``adj_tensors('csc')`` when DGL is installed; it is not required).
+
+``edge_weight`` (every layer's and model's ``forward``; DGL's argument of the same name): an
+f32 ``[E]`` tensor in the CSRGraph's own edge order. As in DGL the degree normalisation comes
+from the unweighted degrees and each edge's message is multiplied by its weight (``u_mul_e``),
+and the output is differentiable in it, on both nonlinear paths: the SDDMM kernel
+(``maxk_sddmm_edge_grad``) gives its gradient, for ``nonlinear="relu"`` run with ``k = D`` on
+the dense features with identity selectors. It needs a CSRGraph: with a DGL graph it raises
+``TypeError``, because the edge-id permutation between the two orders is not mapped.
 """
 from __future__ import annotations
 
@@ -68,9 +76,12 @@ from .autograd import (CSRGraph, dense_aggregate, densify, maxk, maxk_aggregate,
 NONLINEAR = ("maxk", "relu")
 
 
-def as_csr(graph) -> CSRGraph:
+def as_csr(graph, edge_weight=None) -> CSRGraph:
     if isinstance(graph, CSRGraph):
         return graph
+    if edge_weight is not None:
+        raise TypeError("edge_weight needs a maxk_kernels.CSRGraph: the weights follow the "
+                        "CSRGraph's own edge order, and a DGL graph's edge ids are not mapped to it")
     if hasattr(graph, "adj_tensors"):
         return CSRGraph.from_dgl(graph)
     raise TypeError("graph must be a maxk_kernels.CSRGraph or a DGL graph")
@@ -97,16 +108,17 @@ def _maxk_dropout(layer, feat: torch.Tensor):
     return _sparse_dropout(sp_data, layer.feat_drop, layer.training), sp_index
 
 
-def _maxk_self_pair(layer, feat: torch.Tensor, csr: CSRGraph):
+def _maxk_self_pair(layer, feat: torch.Tensor, csr: CSRGraph, edge_weight=None):
     """``(x, A @ x)`` with ``x = feat_drop(MaxK(feat))`` dense, for a layer with a self term:
     ``maxk_self_aggregate`` unless ``F.dropout`` has to sit between MaxK and the aggregation
     (training with ``feat_drop > 0`` and no ``fused_dropout``)."""
     if layer.feat_drop > 0 and layer.training and not layer.fused_dropout:
         sp_data, sp_index = _maxk_dropout(layer, feat)
         return (densify(sp_data, sp_index, layer.in_feats),
-                spgemm(sp_data, sp_index, csr, layer.in_feats))
+                spgemm(sp_data, sp_index, csr, layer.in_feats, edge_weight=edge_weight))
     return maxk_self_aggregate(feat, csr, layer.maxk, layer.topk_mode,
-                               dropout_p=layer.feat_drop, training=layer.training)
+                               dropout_p=layer.feat_drop, training=layer.training,
+                               edge_weight=edge_weight)
 
 
 def _make_norm(norm, out_feats):
@@ -154,26 +166,28 @@ class MaxKSAGEConv(nn.Module):
         if self.bias is not None:
             nn.init.zeros_(self.bias)
 
-    def forward(self, graph, feat: torch.Tensor) -> torch.Tensor:
-        csr = as_csr(graph).with_values(self.aggregator_type)
+    def forward(self, graph, feat: torch.Tensor, edge_weight=None) -> torch.Tensor:
+        ew = edge_weight
+        csr = as_csr(graph, ew).with_values(self.aggregator_type)
         if self.nonlinear == "relu":
             # dglnn.SAGEConv(mean) on dense features (the model applied the ReLU)
             x = F.dropout(feat, self.feat_drop, self.training) if self.feat_drop > 0 else feat
-            rst = self.fc_self(x) + self.fc_neigh(dense_aggregate(x, csr))
+            rst = self.fc_self(x) + self.fc_neigh(dense_aggregate(x, csr, ew))
         elif self.maxk_after_fc:
             # reference ordering (maxk_layers.py:85-88): MaxK(fc_neigh(feat)) aggregated
             h_self = self.fc_self(feat)
             if self.feat_drop > 0 and self.training and self.fused_dropout:
                 rst = h_self + maxk_aggregate(self.fc_neigh(feat), csr, self.maxk, self.topk_mode,
-                                              dropout_p=self.feat_drop)
+                                              dropout_p=self.feat_drop, edge_weight=ew)
             elif self.feat_drop > 0 and self.training:
                 sp_data, sp_index = maxk(self.fc_neigh(feat), self.maxk, self.topk_mode)
                 sp_data = _sparse_dropout(sp_data, self.feat_drop, self.training)
-                rst = h_self + spgemm(sp_data, sp_index, csr, self.out_feats)
+                rst = h_self + spgemm(sp_data, sp_index, csr, self.out_feats, edge_weight=ew)
             else:  # no dropout between MaxK and the SpGEMM: the fused producer-consumer pair
-                rst = h_self + maxk_aggregate(self.fc_neigh(feat), csr, self.maxk, self.topk_mode)
+                rst = h_self + maxk_aggregate(self.fc_neigh(feat), csr, self.maxk, self.topk_mode,
+                                              edge_weight=ew)
         else:
-            x, neigh = _maxk_self_pair(self, feat, csr)
+            x, neigh = _maxk_self_pair(self, feat, csr, ew)
             rst = self.fc_self(x) + self.fc_neigh(neigh)
         if self.bias is not None:
             rst = rst + self.bias
@@ -212,24 +226,27 @@ class MaxKGCNConv(nn.Module):
         if self.bias is not None:
             nn.init.zeros_(self.bias)
 
-    def forward(self, graph, feat: torch.Tensor) -> torch.Tensor:
-        csr = as_csr(graph)
+    def forward(self, graph, feat: torch.Tensor, edge_weight=None) -> torch.Tensor:
+        ew = edge_weight
+        csr = as_csr(graph, ew)
         if not self.allow_zero_in_degree and bool((csr.in_degrees() == 0).any()):
             raise ValueError("Graph has nodes with zero in-degree")
         if self.weight is not None:
             feat = feat @ self.weight
         if self.nonlinear == "relu":
             x = F.dropout(feat, self.feat_drop, self.training) if self.feat_drop > 0 else feat
-            rst = dense_aggregate(x, csr.with_values(self.norm))
+            rst = dense_aggregate(x, csr.with_values(self.norm), ew)
         elif self.feat_drop > 0 and self.training and self.fused_dropout:
             rst = maxk_aggregate(feat, csr.with_values(self.norm), self.maxk, self.topk_mode,
-                                 dropout_p=self.feat_drop)
+                                 dropout_p=self.feat_drop, edge_weight=ew)
         elif self.feat_drop > 0 and self.training:
             sp_data, sp_index = maxk(feat, self.maxk, self.topk_mode)
             sp_data = _sparse_dropout(sp_data, self.feat_drop, self.training)
-            rst = spgemm(sp_data, sp_index, csr.with_values(self.norm), feat.shape[1])
+            rst = spgemm(sp_data, sp_index, csr.with_values(self.norm), feat.shape[1],
+                         edge_weight=ew)
         else:
-            rst = maxk_aggregate(feat, csr.with_values(self.norm), self.maxk, self.topk_mode)
+            rst = maxk_aggregate(feat, csr.with_values(self.norm), self.maxk, self.topk_mode,
+                                 edge_weight=ew)
         if self.bias is not None:
             rst = rst + self.bias
         return rst
@@ -258,12 +275,12 @@ class MaxKGINConv(nn.Module):
         else:
             self.register_buffer("eps", eps)
 
-    def forward(self, graph, feat: torch.Tensor) -> torch.Tensor:
-        csr = as_csr(graph).with_values("sum")
+    def forward(self, graph, feat: torch.Tensor, edge_weight=None) -> torch.Tensor:
+        csr = as_csr(graph, edge_weight).with_values("sum")
         if self.nonlinear == "relu":
             x = F.dropout(feat, self.feat_drop, self.training) if self.feat_drop > 0 else feat
-            return (1 + self.eps) * x + dense_aggregate(x, csr)
-        x, neigh = _maxk_self_pair(self, feat, csr)
+            return (1 + self.eps) * x + dense_aggregate(x, csr, edge_weight)
+        x, neigh = _maxk_self_pair(self, feat, csr, edge_weight)
         return (1 + self.eps) * x + neigh
 
 
@@ -286,12 +303,12 @@ class MaxKSAGE(nn.Module):
         nn.init.xavier_uniform_(self.lin_in.weight)
         nn.init.xavier_uniform_(self.lin_out.weight)
 
-    def forward(self, g, x):
+    def forward(self, g, x, edge_weight=None):
         x = self.lin_in(x)
         for layer in self.layers:
             if self.nonlinear == "relu":
                 x = F.relu(x)
-            x = layer(g, x)
+            x = layer(g, x, edge_weight)
         return self.lin_out(x)
 
 
@@ -318,13 +335,13 @@ class MaxKGCN(nn.Module):
         for lin in [self.lin_in, self.lin_out, *self.linlayers]:
             nn.init.xavier_uniform_(lin.weight)
 
-    def forward(self, g, x):
+    def forward(self, g, x, edge_weight=None):
         x = self.lin_in(x).relu()
         for i, conv in enumerate(self.gcnlayers):
             x = self.linlayers[i](x)
             if self.nonlinear == "relu":
                 x = F.relu(x)
-            x = conv(g, x)
+            x = conv(g, x, edge_weight)
             if self.normlayers is not None:
                 x = self.normlayers[i](x)
         return self.lin_out(x)
@@ -352,13 +369,13 @@ class MaxKGIN(nn.Module):
         for lin in [self.lin_in, self.lin_out, *self.linlayers]:
             nn.init.xavier_uniform_(lin.weight)
 
-    def forward(self, g, x):
+    def forward(self, g, x, edge_weight=None):
         x = self.lin_in(x).relu()
         for i, conv in enumerate(self.ginlayers):
             x = self.linlayers[i](x)
             if self.nonlinear == "relu":
                 x = F.relu(x)
-            x = conv(g, x)
+            x = conv(g, x, edge_weight)
             if self.normlayers is not None:
                 x = self.normlayers[i](x)
         return self.lin_out(x)

@@ -673,6 +673,45 @@ def spgemm_backward(ptr, idx, val, grad_output, sp_index, num_nodes: int, num_ed
     return grad_sp
 
 
+def spgemm_edge_grad(ptr, idx, grad_output, sp_data, sp_index, num_nodes: int, num_edges: int,
+                     dim_k: int, dim_origin: int,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Gradient of :func:`spgemm_forward` with respect to ``val``: the sampled dense-dense
+    product ``grad_val[e] = sum_l sp_data[c, l] * grad_output[r, sp_index[c, l]]`` for edge
+    ``e = (r, c)``, f32 ``[num_edges]`` in CSR edge order (``maxk_sddmm_edge_grad``; the
+    summation order is pinned in include/maxk_hip.h). It depends on neither ``val`` nor a
+    plan. ``grad_output`` is ``[num_nodes, dim_origin]`` (rows may be strided); the tables have
+    one row per source column (their row count is the number of columns, so a rectangular
+    shard works) and may be strided, e.g. interleaved records. ``out``: a contiguous f32
+    ``[num_edges]`` tensor to write into."""
+    _check_tensor(ptr, "ptr", torch.int32)
+    _check_tensor(idx, "idx", torch.int32)
+    _need(ptr.dim() == 1 and ptr.numel() == num_nodes + 1, "ptr must have num_nodes+1 entries")
+    _need(idx.numel() == num_edges, "idx must have num_edges entries")
+    _need(1 <= dim_k <= dim_origin <= 256, "k must be between 1 and input dimension")
+    _need(isinstance(sp_data, torch.Tensor) and sp_data.dim() == 2,
+          "sp_data must be [num_cols, dim_k]")
+    num_cols = sp_data.shape[0]
+    gs = _table(grad_output, "grad_output", torch.float32, num_nodes, dim_origin)
+    ds = _table(sp_data, "sp_data", torch.float32, num_cols, dim_k)
+    is_ = _table(sp_index, "sp_index", torch.uint8, num_cols, dim_k)
+    dev = ptr.device
+    _need(idx.device == dev and grad_output.device == dev and sp_data.device == dev and
+          sp_index.device == dev, "all tensors must be on the same device")
+    if out is None:
+        out = torch.empty(num_edges, dtype=torch.float32, device=dev)
+    else:
+        _check_tensor(out, "out", torch.float32)
+        _need(out.dim() == 1 and out.numel() == num_edges and out.device == dev,
+              "out must be [num_edges] on the graph's device")
+    with _device(dev):
+        check(lib.maxk_sddmm_edge_grad(_p(ptr), _p(idx), _p(grad_output), gs, _p(sp_data), ds,
+                                       _p(sp_index), is_, _p(out), num_nodes, num_cols,
+                                       num_edges, dim_origin, dim_k, _stream()),
+              "spgemm_edge_grad")
+    return out
+
+
 def plan_col_order(plan: GraphPlan) -> torch.Tensor:
     """The plan's column order: int32 [num_cols], position -> column of the backward's column
     blocks (the identity for plans without one)."""

@@ -13,6 +13,10 @@ formula (the SSpMM backward) as a registered derivative.
                                   dim_k, dim_origin) -> out [num_nodes, dim_origin]
     torch.ops.maxk.spgemm_backward(ptr, idx, val, grad_output, sp_index, num_nodes,
                                    num_edges, dim_k, dim_origin) -> grad_sp [num_nodes, dim_k]
+    torch.ops.maxk.spgemm_edge_grad(ptr, idx, grad_output, sp_data, sp_index, num_nodes,
+                                    num_edges, dim_k, dim_origin) -> grad_val [num_edges]
+                                  (what spgemm_forward's derivative returns for a val that
+                                   requires grad)
 
     torch.ops.maxk.maxk_dropout_forward(input, k, p, seed) -> (sp_data, sp_index)
     torch.ops.maxk.maxk_dropout_backward(grad_output, indices, dim_origin, p, seed)
@@ -93,17 +97,37 @@ def _(ptr, idx, val, grad_output, sp_index, num_nodes, num_edges, dim_k, dim_ori
     return grad_output.new_empty((num_nodes, dim_k))
 
 
+@torch.library.custom_op(f"{_NS}::spgemm_edge_grad", mutates_args=())
+def spgemm_edge_grad(ptr: torch.Tensor, idx: torch.Tensor, grad_output: torch.Tensor,
+                     sp_data: torch.Tensor, sp_index: torch.Tensor, num_nodes: int,
+                     num_edges: int, dim_k: int, dim_origin: int) -> torch.Tensor:
+    """SDDMM ``grad_val[e] = sum_l sp_data[c, l] * grad_output[r, sp_index[c, l]]``, the
+    gradient of ``spgemm_forward`` with respect to ``val`` (ops.spgemm_edge_grad)."""
+    return ops.spgemm_edge_grad(ptr, idx, grad_output, sp_data, sp_index, num_nodes, num_edges,
+                                dim_k, dim_origin)
+
+
+@spgemm_edge_grad.register_fake
+def _(ptr, idx, grad_output, sp_data, sp_index, num_nodes, num_edges, dim_k, dim_origin):
+    return grad_output.new_empty((num_edges,))
+
+
 def _spgemm_setup(ctx, inputs, output):
-    ptr, idx, val, _, sp_index, num_nodes, num_edges, dim_k, dim_origin = inputs
-    ctx.save_for_backward(ptr, idx, val, sp_index)
+    ptr, idx, val, sp_data, sp_index, num_nodes, num_edges, dim_k, dim_origin = inputs
+    # the value table is saved only for a val that needs a gradient
+    ctx.save_for_backward(ptr, idx, val, sp_index, *((sp_data,) if ctx.needs_input_grad[2] else ()))
     ctx.dims = (num_nodes, num_edges, dim_k, dim_origin)
 
 
 def _spgemm_backward(ctx, grad):
-    ptr, idx, val, sp_index = ctx.saved_tensors
-    grad_sp = torch.ops.maxk.spgemm_backward(ptr, idx, val, grad.contiguous(), sp_index,
-                                             *ctx.dims)
-    return None, None, None, grad_sp, None, None, None, None, None
+    ptr, idx, val, sp_index = ctx.saved_tensors[:4]
+    grad = grad.contiguous()
+    grad_sp = torch.ops.maxk.spgemm_backward(ptr, idx, val, grad, sp_index, *ctx.dims)
+    grad_val = None
+    if ctx.needs_input_grad[2]:
+        grad_val = torch.ops.maxk.spgemm_edge_grad(ptr, idx, grad, ctx.saved_tensors[4], sp_index,
+                                                   *ctx.dims)
+    return None, None, grad_val, grad_sp, None, None, None, None, None
 
 
 spgemm_forward.register_autograd(_spgemm_backward, setup_context=_spgemm_setup)

@@ -22,7 +22,15 @@ against the composition maxk -> densify -> spgemm (with F.dropout on the [N, k] 
 --dropout) in the same process, the composition before and after the fused step, each step's
 peak memory, and the dense top-k / merge scatter kernels next to the plain ones.
 
+Round 10: --edge-weight times the step with a learnable per-edge weight
+(maxk_aggregate(x, graph, k, edge_weight=w), w [E] requiring grad) against the constant-weight
+step in the same process, the constant step before and after, and separately the passes the
+weighted step adds: the effective-value multiply and its backward, the value refresh of the
+weighted plan (forward-only, since the backward re-refreshes only after another weighted call),
+and the SDDMM edge-gradient kernel.
+
   python tools/autograd_step.py [--dataset reddit] [--k 16] [--dropout 0.5] [--self]
+                                [--edge-weight]
   rocprofv3 --kernel-trace --stats ... -- python tools/autograd_step.py --only-step 20
     (nothing but 20 maxk_aggregate steps: the kernel list of the fused step)
 """
@@ -121,6 +129,51 @@ def dropout_report(args, graph, x, g, d, k, step_dropout, step_composed):
                       "peak_bytes_saved": mem_comp - mem_fused, "kernels": kern}), flush=True)
 
 
+def edge_weight_report(args, graph, x, g, d, k, step_fresh):
+    dev, n, e = x.device, x.shape[0], graph.num_edges
+    w = (torch.rand(e, device=dev) + 0.5).requires_grad_(True)
+
+    def step_weighted():
+        x.grad = None
+        w.grad = None
+        y = mk.maxk_aggregate(x, graph, k, edge_weight=w)
+        y.backward(g)
+
+    t_const1 = timeit(step_fresh)
+    t_w = timeit(step_weighted)
+    t_const2 = timeit(step_fresh)
+    t_w2 = timeit(step_weighted)
+    t_host = host_time(step_weighted)
+    mem_w, mem_const = peak_bytes(step_weighted), peak_bytes(step_fresh)
+    plan = graph.weighted_plan(d, k)
+    sp_data, sp_index = mk.maxk_forward(x.detach(), k, return_index=True)
+    val = (graph.val * w).detach()
+    gval = torch.empty(e, device=dev)
+    parts = {
+        "refresh_values_ms": timeit(lambda: plan.refresh_values(val)),
+        "sddmm_edge_grad_ms": timeit(lambda: mk.spgemm_edge_grad(
+            graph.ptr, graph.idx, g, sp_data, sp_index, n, e, k, d, out=gval)),
+        "effective_values_mul_ms": timeit(lambda: graph.val * w.detach()),
+        "mul_backward_ms": timeit(lambda: gval * graph.val),
+    }
+    rec = plan.new_records()
+    if rec is not None:  # the weighted top-k also writes the plain value table (for the SDDMM)
+        xd = x.detach()
+        parts["topk_values_table_extra_ms"] = (
+            timeit(lambda: mk.maxk_forward(xd, k, return_index=True, records=rec))
+            - timeit(lambda: mk.maxk_forward(xd, k, return_index=True, records=rec,
+                                             return_values=False)))
+    print(json.dumps({"dataset": args.dataset, "k": k, "edge_weight": True,
+                      "fwd_layout": plan.info()["fwd_layout"], "fwd_fixed": int(plan.fwd_fixed),
+                      "step_ms_edge_weight": t_w, "step_ms_edge_weight_again": t_w2,
+                      "step_ms_constant": [t_const1, t_const2],
+                      "added_ms": t_w - min(t_const1, t_const2),
+                      "host_ms_per_step_edge_weight": t_host,
+                      "peak_bytes_edge_weight": mem_w, "peak_bytes_constant": mem_const,
+                      "added_parts": parts, "added_parts_sum_ms": sum(parts.values())}),
+          flush=True)
+
+
 def self_report(args, graph, x, g, g_self, d, k, step_self, step_self_composed):
     p, dev, n = args.dropout, x.device, x.shape[0]
     t_comp1 = timeit(step_self_composed)
@@ -185,6 +238,8 @@ def main():
     ap.add_argument("--self", dest="self_term", action="store_true",
                     help="time maxk_self_aggregate (dense masked row + aggregation) against "
                          "maxk -> densify -> spgemm")
+    ap.add_argument("--edge-weight", dest="edge_weight", action="store_true",
+                    help="time the step with a learnable edge_weight against the constant one")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     n, _ = graphs.DATASETS[args.dataset]
@@ -251,6 +306,9 @@ def main():
                           "dropout": p_drop, "self": args.self_term,
                           "fwd_layout": info["fwd_layout"], "fwd_fixed": info["fwd_fixed"],
                           "fwd_split_rows": info["fwd_split_rows"]}), flush=True)
+        return
+    if args.edge_weight:
+        edge_weight_report(args, graph, x, g, d, k, step_fresh)
         return
     if args.self_term:
         self_report(args, graph, x, g, g_self, d, k, step_self, step_self_composed)
