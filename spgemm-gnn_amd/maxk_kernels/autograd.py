@@ -566,12 +566,17 @@ def densify(sp_data: torch.Tensor, sp_index: torch.Tensor, dim_origin: int) -> t
 def _dropout_pair(dropout_p: float, training: bool, seed):
     """The ``(p, seed)`` pair of a fused-dropout call, or ``None`` when nothing is dropped.
     ``seed=None`` draws one int64 from torch's CPU default generator: reproducible under
-    ``torch.manual_seed``, and no device sync."""
+    ``torch.manual_seed``, and no device sync. The seed is a launch argument, so a step captured
+    into a graph replays the mask of capture time: an explicit ``seed`` means exactly that and
+    is accepted; drawing one during capture is refused (``F.dropout``, which the fused dropout
+    replaces, draws a fresh mask on every replay)."""
     if not training or dropout_p == 0:
         return None
     if not 0.0 <= dropout_p <= 1.0:
         raise ValueError(f"dropout probability has to be between 0 and 1, but got {dropout_p}")
     if seed is None:
+        ops._refuse_capture("fused dropout with seed=None (a seed drawn on the host)",
+                            "pass seed=; a captured step replays one mask")
         seed = torch.empty((), dtype=torch.int64).random_().item()
     return float(dropout_p), int(seed)
 

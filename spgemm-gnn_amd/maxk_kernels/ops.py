@@ -51,6 +51,14 @@ def _need(cond: bool, msg: str) -> None:
         raise RuntimeError(msg)
 
 
+def _refuse_capture(what: str, remedy: str) -> None:
+    """Raises while the current stream is being captured into a graph, before any launch, event
+    or allocation: for the calls whose host-side work (a plan build, a value refresh, a drawn
+    seed) a replay would silently skip. Not used on the compute path, which costs no query."""
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(f"{what} cannot run while a graph is being captured: {remedy}")
+
+
 def _check_tensor(t: torch.Tensor, name: str, dtype: Optional[torch.dtype] = None) -> None:
     _need(isinstance(t, torch.Tensor), f"{name} must be a tensor")
     _need(t.is_cuda, f"{name} must be a CUDA tensor")
@@ -314,7 +322,10 @@ class GraphPlan:
         """``options``: ``maxk_plan_options`` fields by name (``col_order`` also by name:
         'identity', 'scattered'; ``bwd_algo``: 'column_blocks', 'two_pass'); ``col_order``: an
         int32 device permutation of the columns (position -> column) for the backward's
-        column blocks, which selects ``col_order='given'``."""
+        column blocks, which selects ``col_order='given'``. Building allocates and synchronises
+        the stream, so it is refused while a graph is being captured."""
+        _refuse_capture("GraphPlan (building a plan)",
+                        "build the plan before capture (call once eagerly)")
         self.handle = ctypes.c_void_p(0)
         self.device = ptr.device
         self._refs = (ptr, idx, val)  # keep the graph's storage alive while cached
@@ -478,7 +489,13 @@ class GraphPlan:
 
     def refresh_values(self, val: torch.Tensor) -> None:
         """Re-snapshot in-place-modified edge values (same tensor, new ``_version``); runs
-        after every earlier use of the plan on any stream."""
+        after every earlier use of the plan on any stream. It allocates stream-ordered scratch
+        and orders itself across streams with events, and a replay would skip its host
+        bookkeeping, so it is refused while a graph is being captured (that covers
+        ``edge_weight=`` and :func:`get_plan` after an in-place edit of ``val``)."""
+        _refuse_capture("GraphPlan.refresh_values (edge_weight=, or edge values edited in place)",
+                        "a captured step computes with the edge values of capture time; refresh "
+                        "the plan outside the capture and capture again")
         stream = torch.cuda.current_stream(self.device)
         with self._lock:
             for other in self._uses.values():
