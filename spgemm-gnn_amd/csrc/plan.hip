@@ -1104,6 +1104,16 @@ static int plan_create_impl(const int32_t* ptr, const int32_t* idx, const float*
       return ke;
     };
     PLAN_TRY(sort_blocks(row_hash));
+    // the key kernel has validated every column id (clamping the ones it indexed with): refuse
+    // a bad idx here, before any kernel indexes with an unclamped one (gather_bwd_kernel reads
+    // colpos[idx[e]] under a column order)
+    int bad = 0;
+    PLAN_TRY(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    PLAN_TRY(hipStreamSynchronize(s));
+    if (bad) {
+      set_error("maxk_plan_create: idx contains column ids outside [0, num_cols)");
+      return fail(MAXK_ERR_INVALID_ARG);
+    }
     if (row_hash_ok && o.bwd_row_order == 0) {
       // auto: scatter the rows when the ascending-row streams are mostly dense runs, i.e. many
       // consecutive rows with many edges into the same block (an ID-ordered community: Reddit
@@ -1177,8 +1187,6 @@ static int plan_create_impl(const int32_t* ptr, const int32_t* idx, const float*
     hipLaunchKernelGGL(key_offsets_kernel, dim3(nblocks / 256 + 1), dim3(256), 0, s, keys_out,
                        E, nblocks, d_offs);
     PLAN_TRY(hipGetLastError());
-    int bad = 0;
-    PLAN_TRY(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
     if (twopass) {
       // column pointers of the column-sorted edge list stay on the device
       p->bwd_colptr = d_offs;
@@ -1211,10 +1219,6 @@ static int plan_create_impl(const int32_t* ptr, const int32_t* idx, const float*
                               hipMemcpyDeviceToHost, s));
       PLAN_TRY(hipStreamSynchronize(s));
       for (int b = 0; b <= nblocks; ++b) offs[b] = offs32[b];
-    }
-    if (bad) {
-      set_error("maxk_plan_create: idx contains column ids outside [0, num_cols)");
-      return fail(MAXK_ERR_INVALID_ARG);
     }
   }
   std::vector<BwdTask> btasks;

@@ -594,7 +594,14 @@ def _cache_budget(device) -> int:
 
 def get_plan(ptr, idx, val, num_nodes, num_edges, dim_origin, dim_k) -> GraphPlan:
     """Cached plan for (graph storage, structure version, value tensor, k, D); in-place
-    edits of ``val`` (a new ``val._version``) refresh the plan's value snapshot."""
+    edits of ``val`` (a new ``val._version``) refresh the plan's value snapshot.
+
+    The key is ``(device, ptr/idx data_ptr, ptr/idx _version, val data_ptr, N, E, D, k)``, so an
+    edit is seen only through torch's version counter. Edits that bypass it are unsupported:
+    after ``idx.data.copy_(...)`` (``.data`` has a version counter of its own), or a write
+    through a raw pointer, the cached plan of the old structure or values keeps being served.
+    Call :func:`clear_plan_cache` after such an edit, or edit the tensor itself
+    (``idx.copy_(...)``, ``val.mul_(...)``)."""
     key = (ptr.device.index, ptr.data_ptr(), idx.data_ptr(), ptr._version, idx._version,
            val.data_ptr(), int(num_nodes), int(num_edges), int(dim_origin), int(dim_k))
     with _PLAN_LOCK:
