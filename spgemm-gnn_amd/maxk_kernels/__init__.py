@@ -20,6 +20,8 @@ from .ops import (  # noqa: F401
     cbsr_stats,
     clear_plan_cache,
     dense_spmm,
+    edge_softmax_backward,
+    edge_softmax_row_limits,
     get_plan,
     maxk_backward,
     maxk_forward,
@@ -32,6 +34,7 @@ from .autograd import (  # noqa: F401
     CSRGraph,
     DenseAggFunction,
     DenseEdgeWeightedFunction,
+    EdgeSoftmaxFunction,
     EdgeWeightedFunction,
     MaxKAggregateFunction,
     MaxKFunction,
@@ -39,6 +42,7 @@ from .autograd import (  # noqa: F401
     SpGEMMFunction,
     dense_aggregate,
     densify,
+    edge_softmax,
     maxk,
     maxk_aggregate,
     maxk_self_aggregate,
@@ -48,6 +52,7 @@ from .autograd import (  # noqa: F401
 from . import torch_ops  # noqa: F401,E402  (registers torch.ops.maxk.*)
 from .layers import (  # noqa: F401,E402
     MaxKGCN,
+    MaxKGATConv,
     MaxKGCNConv,
     MaxKGIN,
     MaxKGINConv,
@@ -62,6 +67,8 @@ __all__ = [
     "densify", "MaxKSAGEConv", "MaxKGCNConv", "MaxKGINConv", "MaxKSAGE", "MaxKGCN",
     "MaxKGIN", "dense_aggregate", "DenseAggFunction", "MaxKSelfAggregateFunction",
     "maxk_self_aggregate", "spgemm_edge_grad", "EdgeWeightedFunction", "DenseEdgeWeightedFunction",
+    "edge_softmax", "edge_softmax_backward", "edge_softmax_row_limits", "EdgeSoftmaxFunction",
+    "MaxKGATConv",
 ]
 
 ABI_VERSION = lib.maxk_abi_version()

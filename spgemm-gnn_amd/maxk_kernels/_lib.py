@@ -83,6 +83,9 @@ SIGNATURES = {
                                                  ctypes.POINTER(_i64)]),
     "maxk_sddmm_edge_grad": (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32,
                                             _i32, _i64, _i32, _i32, _vp]),
+    "maxk_edge_softmax_forward": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i64, _vp]),
+    "maxk_edge_softmax_backward": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i64, _vp]),
+    "maxk_edge_softmax_row_limits": (ctypes.c_int, [_vp, _i32]),
     "maxk_dense_spmm_csr": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "maxk_warp4_build": (ctypes.c_int, [_vp, _i32, _i32, _vp, _i64, ctypes.POINTER(_i64)]),
 }

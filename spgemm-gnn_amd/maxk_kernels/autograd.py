@@ -15,6 +15,8 @@ module that does not exist) and its ``MaxKFunction`` (utils/maxk_layers.py:16-45
   input (``edge_weight=`` on :func:`spgemm`, :func:`maxk_aggregate`,
   :func:`maxk_self_aggregate`): the same kernels on a value-refreshed plan, plus the SDDMM
   ``ops.spgemm_edge_grad`` for the values' gradient.
+* :class:`EdgeSoftmaxFunction` (:func:`edge_softmax`) normalises per-edge logits over each
+  destination row's in-edges: the attention weights that ``edge_weight=`` then takes.
 """
 from __future__ import annotations
 
@@ -110,6 +112,16 @@ class CSRGraph:
 
     def out_degrees(self) -> torch.Tensor:
         return torch.bincount(self.idx.to(torch.int64), minlength=self.num_nodes)
+
+    def edge_rows(self) -> torch.Tensor:
+        """The destination row of every edge, int64 ``[E]`` in CSR edge order (cached): the
+        row-side gather index of a per-edge score such as ``er[edge_rows]``."""
+        rows = self._values.get("edge_rows")
+        if rows is None:
+            rows = torch.repeat_interleave(torch.arange(self.num_nodes, device=self.device),
+                                           self.in_degrees(), output_size=self.num_edges)
+            self._values["edge_rows"] = rows
+        return rows
 
     def edge_values(self, kind: str) -> torch.Tensor:
         """Per-edge weights for the aggregation ``kind`` (cached):
@@ -534,6 +546,39 @@ class DenseEdgeWeightedFunction(torch.autograd.Function):
             grad_val = ops.spgemm_edge_grad(graph.ptr, graph.idx, grad_out, x, ident, n,
                                             graph.num_edges, d, d)
         return grad_x, grad_val, None
+
+
+class EdgeSoftmaxFunction(torch.autograd.Function):
+    """Softmax of per-edge logits over each destination row's in-edges (DGL's
+    ``edge_softmax``): ``ops.edge_softmax`` forward, ``ops.edge_softmax_backward`` backward. Only
+    the output is saved: the gradient ``y * (g - sum_row(y g))`` needs no logits."""
+
+    @staticmethod
+    def forward(ctx, graph: CSRGraph, logits: torch.Tensor):
+        y = ops.edge_softmax(graph.ptr, logits.contiguous())
+        ctx.save_for_backward(y)
+        ctx.graph = graph
+        ctx.set_materialize_grads(False)  # an unused output arrives as None, not as zeros
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        if grad_y is None or not ctx.needs_input_grad[1]:
+            return None, None
+        (y,) = ctx.saved_tensors
+        return None, ops.edge_softmax_backward(ctx.graph.ptr, y, grad_y.contiguous())
+
+
+def edge_softmax(graph: CSRGraph, logits: torch.Tensor) -> torch.Tensor:
+    """``alpha[e] = exp(logits[e]) / sum_{e' into row(e)} exp(logits[e'])`` for f32 ``[E]``
+    logits in the CSRGraph's own edge order, differentiable in ``logits`` (DGL's
+    ``edge_softmax`` over the in-edges; EdgeSoftmaxFunction). The result is an ``edge_weight=``
+    of the aggregations: attention."""
+    if not (isinstance(logits, torch.Tensor) and logits.dtype == torch.float32 and
+            logits.shape == (graph.num_edges,) and logits.device == graph.device):
+        raise RuntimeError("logits must be a float32 [num_edges] tensor on the graph's device, "
+                           "in the CSRGraph's edge order")
+    return EdgeSoftmaxFunction.apply(graph, logits)
 
 
 def _effective_values(graph: CSRGraph, edge_weight: torch.Tensor) -> torch.Tensor:

@@ -63,6 +63,10 @@ and the output is differentiable in it, on both nonlinear paths: the SDDMM kerne
 (``maxk_sddmm_edge_grad``) gives its gradient, for ``nonlinear="relu"`` run with ``k = D`` on
 the dense features with identity selectors. It needs a CSRGraph: with a DGL graph it raises
 ``TypeError``, because the edge-id permutation between the two orders is not mapped.
+
+``MaxKGATConv`` is the layer that ``edge_weight=`` and the edge softmax (``edge_softmax``,
+``maxk_edge_softmax_forward`` / ``_backward``) make possible: single-head graph attention
+(``dglnn.GATConv`` with one head) whose messages are the MaxK features.
 """
 from __future__ import annotations
 
@@ -70,7 +74,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .autograd import (CSRGraph, dense_aggregate, densify, maxk, maxk_aggregate,
+from .autograd import (CSRGraph, dense_aggregate, densify, edge_softmax, maxk, maxk_aggregate,
                        maxk_self_aggregate, spgemm)
 
 NONLINEAR = ("maxk", "relu")
@@ -247,6 +251,78 @@ class MaxKGCNConv(nn.Module):
         else:
             rst = maxk_aggregate(feat, csr.with_values(self.norm), self.maxk, self.topk_mode,
                                  edge_weight=ew)
+        if self.bias is not None:
+            rst = rst + self.bias
+        return rst
+
+
+class MaxKGATConv(nn.Module):
+    """Single-head graph attention (``dglnn.GATConv(num_heads=1)`` without residual or
+    activation) on MaxK features, ``[N, in_feats] -> [N, out_feats]``:
+
+        h = fc(feat);  el = <h, attn_l>;  er = <h, attn_r>        (the dense h, before MaxK)
+        e_uv = leaky_relu(el_u + er_v);  alpha = attn_drop(edge_softmax(e))
+        rst_v = sum_{u->v} alpha_uv * feat_drop(MaxK(h))_u + bias
+
+    The softmax over each node's in-edges is the HIP pair behind :func:`edge_softmax`, the
+    aggregation ``maxk_aggregate(..., edge_weight=alpha)`` on the unit-valued graph with the
+    ``feat_drop`` / ``fused_dropout`` branches of :class:`MaxKGCNConv`; ``nonlinear="relu"``
+    aggregates the dense ``h`` (``dense_aggregate``). The score gather ``el[idx] +
+    er[edge_rows]`` and its gradient are torch's. The attention needs the CSRGraph's own edge
+    order, so a DGL graph raises the ``TypeError`` of ``edge_weight=``."""
+
+    def __init__(self, in_feats, out_feats, maxk=32, negative_slope=0.2, attn_drop=0.,
+                 feat_drop=0., bias=True, allow_zero_in_degree=False, topk_mode="exact",
+                 nonlinear="maxk", fused_dropout=False):
+        super().__init__()
+        self.fused_dropout = bool(fused_dropout)
+        self.in_feats = in_feats
+        self.out_feats = out_feats
+        self.maxk = maxk
+        self.negative_slope = float(negative_slope)
+        self.attn_drop = float(attn_drop)
+        self.feat_drop = float(feat_drop)
+        self.allow_zero_in_degree = allow_zero_in_degree
+        self.topk_mode = topk_mode
+        self.nonlinear = _check_nonlinear(nonlinear)
+        self.fc = nn.Linear(in_feats, out_feats, bias=False)
+        self.attn_l = nn.Parameter(torch.empty(1, out_feats))
+        self.attn_r = nn.Parameter(torch.empty(1, out_feats))
+        self.bias = nn.Parameter(torch.empty(out_feats)) if bias else None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        gain = nn.init.calculate_gain("relu")
+        nn.init.xavier_normal_(self.fc.weight, gain=gain)
+        nn.init.xavier_normal_(self.attn_l, gain=gain)
+        nn.init.xavier_normal_(self.attn_r, gain=gain)
+        if self.bias is not None:
+            nn.init.zeros_(self.bias)
+
+    def forward(self, graph, feat: torch.Tensor) -> torch.Tensor:
+        csr = as_csr(graph, True)  # attention weights are an edge_weight: CSRGraph only
+        if not self.allow_zero_in_degree and bool((csr.in_degrees() == 0).any()):
+            raise ValueError("Graph has nodes with zero in-degree")
+        h = self.fc(feat)
+        el = (h * self.attn_l).sum(-1)
+        er = (h * self.attn_r).sum(-1)
+        e = F.leaky_relu(el[csr.idx] + er[csr.edge_rows()], self.negative_slope)
+        alpha = edge_softmax(csr, e)
+        if self.attn_drop > 0:
+            alpha = F.dropout(alpha, self.attn_drop, self.training)
+        g = csr.with_values("sum")
+        if self.nonlinear == "relu":
+            x = F.dropout(h, self.feat_drop, self.training) if self.feat_drop > 0 else h
+            rst = dense_aggregate(x, g, alpha)
+        elif self.feat_drop > 0 and self.training and self.fused_dropout:
+            rst = maxk_aggregate(h, g, self.maxk, self.topk_mode, dropout_p=self.feat_drop,
+                                 edge_weight=alpha)
+        elif self.feat_drop > 0 and self.training:
+            sp_data, sp_index = maxk(h, self.maxk, self.topk_mode)
+            sp_data = _sparse_dropout(sp_data, self.feat_drop, self.training)
+            rst = spgemm(sp_data, sp_index, g, self.out_feats, edge_weight=alpha)
+        else:
+            rst = maxk_aggregate(h, g, self.maxk, self.topk_mode, edge_weight=alpha)
         if self.bias is not None:
             rst = rst + self.bias
         return rst

@@ -736,6 +736,63 @@ def spgemm_edge_grad(ptr, idx, grad_output, sp_data, sp_index, num_nodes: int, n
     return out
 
 
+def _edge_softmax_args(ptr, tensors, names, out):
+    """The checks shared by :func:`edge_softmax` and :func:`edge_softmax_backward`: ``ptr`` int32
+    ``[num_rows + 1]``, every tensor of ``tensors`` contiguous f32 ``[num_edges]`` on ``ptr``'s
+    device. Returns ``(num_rows, num_edges, out)``."""
+    _check_tensor(ptr, "ptr", torch.int32)
+    _need(ptr.dim() == 1 and ptr.numel() >= 1, "ptr must have num_rows+1 entries")
+    dev = ptr.device
+    num_edges = None
+    for t, name in zip(tensors, names):
+        _check_tensor(t, name, torch.float32)
+        _need(t.dim() == 1, f"{name} must be [num_edges]")
+        num_edges = t.numel() if num_edges is None else num_edges
+        _need(t.numel() == num_edges, f"{name} must have num_edges entries")
+        _need(t.device == dev, "all tensors must be on the same device")
+    if out is None:
+        out = torch.empty(num_edges, dtype=torch.float32, device=dev)
+    else:
+        _check_tensor(out, "out", torch.float32)
+        _need(out.dim() == 1 and out.numel() == num_edges and out.device == dev,
+              "out must be [num_edges] on the graph's device")
+    return ptr.numel() - 1, num_edges, out
+
+
+def edge_softmax(ptr, logits, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Softmax of the per-edge ``logits`` (f32 ``[num_edges]``, CSR edge order) over each
+    destination row's in-edges ``[ptr[r], ptr[r + 1])``: DGL's ``edge_softmax`` on the in-edge
+    CSR (``maxk_edge_softmax_forward``; semantics and accuracy in include/maxk_hip.h, "Edge
+    softmax"). ``ptr[-1] == num_edges`` is a precondition (it is not read on the host).
+    ``out``: a contiguous f32 ``[num_edges]`` tensor to write into."""
+    n, e, out = _edge_softmax_args(ptr, (logits,), ("logits",), out)
+    with _device(ptr.device):
+        check(lib.maxk_edge_softmax_forward(_p(ptr), _p(logits), _p(out), n, e, _stream()),
+              "edge_softmax")
+    return out
+
+
+def edge_softmax_backward(ptr, y, grad_y, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Gradient of :func:`edge_softmax` with respect to the logits, from its output ``y`` and
+    the gradient ``grad_y`` of that output: ``y * (grad_y - sum_row(y * grad_y))``
+    (``maxk_edge_softmax_backward``)."""
+    n, e, out = _edge_softmax_args(ptr, (y, grad_y), ("y", "grad_y"), out)
+    with _device(ptr.device):
+        check(lib.maxk_edge_softmax_backward(_p(ptr), _p(y), _p(grad_y), _p(out), n, e,
+                                             _stream()), "edge_softmax_backward")
+    return out
+
+
+def edge_softmax_row_limits() -> Tuple[int, ...]:
+    """The row lengths at which the edge-softmax kernels switch regime, ascending
+    (``maxk_edge_softmax_row_limits``): a row of exactly a limit's length runs in the regime
+    below it."""
+    count = lib.maxk_edge_softmax_row_limits(None, 0)
+    buf = (ctypes.c_int32 * count)()
+    lib.maxk_edge_softmax_row_limits(ctypes.cast(buf, ctypes.c_void_p), count)
+    return tuple(int(v) for v in buf)
+
+
 def plan_col_order(plan: GraphPlan) -> torch.Tensor:
     """The plan's column order: int32 [num_cols], position -> column of the backward's column
     blocks (the identity for plans without one)."""

@@ -18,6 +18,10 @@ formula (the SSpMM backward) as a registered derivative.
                                   (what spgemm_forward's derivative returns for a val that
                                    requires grad)
 
+    torch.ops.maxk.edge_softmax(ptr, logits) -> [num_edges]   (softmax over each row's in-edges,
+                                  with its registered derivative)
+    torch.ops.maxk.edge_softmax_backward(ptr, y, grad_y) -> grad_logits [num_edges]
+
     torch.ops.maxk.maxk_dropout_forward(input, k, p, seed) -> (sp_data, sp_index)
     torch.ops.maxk.maxk_dropout_backward(grad_output, indices, dim_origin, p, seed)
                                   -> [N, dim_origin]   (MaxK with fused feature dropout)
@@ -131,6 +135,42 @@ def _spgemm_backward(ctx, grad):
 
 
 spgemm_forward.register_autograd(_spgemm_backward, setup_context=_spgemm_setup)
+
+
+@torch.library.custom_op(f"{_NS}::edge_softmax", mutates_args=())
+def edge_softmax(ptr: torch.Tensor, logits: torch.Tensor) -> torch.Tensor:
+    """Softmax of per-edge logits over each destination row's in-edges (ops.edge_softmax)."""
+    return ops.edge_softmax(ptr, logits)
+
+
+@edge_softmax.register_fake
+def _(ptr, logits):
+    return logits.new_empty(logits.shape)
+
+
+@torch.library.custom_op(f"{_NS}::edge_softmax_backward", mutates_args=())
+def edge_softmax_backward(ptr: torch.Tensor, y: torch.Tensor,
+                          grad_y: torch.Tensor) -> torch.Tensor:
+    """``y * (grad_y - sum_row(y * grad_y))``, the gradient of ``edge_softmax`` from its output
+    (ops.edge_softmax_backward)."""
+    return ops.edge_softmax_backward(ptr, y, grad_y)
+
+
+@edge_softmax_backward.register_fake
+def _(ptr, y, grad_y):
+    return y.new_empty(y.shape)
+
+
+def _edge_softmax_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0], output)  # the output only: the backward reads no logits
+
+
+def _edge_softmax_backward(ctx, grad):
+    ptr, y = ctx.saved_tensors
+    return None, torch.ops.maxk.edge_softmax_backward(ptr, y, grad.contiguous())
+
+
+edge_softmax.register_autograd(_edge_softmax_backward, setup_context=_edge_softmax_setup)
 
 
 def _maxk_setup(ctx, inputs, output):
