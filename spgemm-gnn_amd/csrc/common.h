@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "device_buf.h"
 #include "maxk_hip.h"
 
 namespace maxk {
@@ -193,25 +194,25 @@ struct maxk_plan {
   int32_t fwd_waves = 4;        // wavefronts per forward work-group (4 or 8)
   int32_t fwd_unroll = 8;       // forward sub-steps in flight per wave (4 only with 8 waves)
   int32_t fwd_rec_bytes = 0;     // packed CBSR record size (per-call pack)
-  uint8_t* fwd_rec = nullptr;    // [num_cols][fwd_rec_bytes] plan-owned workspace
+  maxk::DeviceBuf<uint8_t> fwd_rec;  // [num_cols][fwd_rec_bytes] plan-owned workspace
   // fixed-point forward (LdsFix): per task {sexp, gexp} (fwd_fix_stats_kernel); the call's
   // {max |x|, min |x|} words live at fwd_xstat_off of the forward workspace
   int32_t fwd_fixed = 0;
-  int2* fwd_fix = nullptr;
-  int32_t* fwd_rowptr = nullptr;  // plan copy of ptr for the bounds' row sums
+  maxk::DeviceBuf<int2> fwd_fix;
+  maxk::DeviceBuf<int32_t> fwd_rowptr;  // plan copy of ptr for the bounds' row sums
   int64_t fwd_xstat_off = 0;
-  maxk::FwdTask* fwd_tasks = nullptr;   // e0/e1 index the permuted edge order below
+  maxk::DeviceBuf<maxk::FwdTask> fwd_tasks;  // e0/e1 index the permuted edge order below
   int32_t fwd_phases = 1;        // column windows of the rotated sweep (1: no rotation)
   int32_t fwd_rot_ticks = 0;     // > 0: rotated sweeps, s_memrealtime ticks per window
   int32_t fwd_chunk3 = 0;        // lane-chunk records: 3 values + their selectors per 16 B
   int32_t fwd_chunk2 = 0;        // pair-chunk records: 2 values + their selectors per 16 B
   int32_t fwd_quad = 0;          // quad-shared edge-word loads
   int32_t fwd_two_tables = 0;    // gather from sp_data / sp_index directly (no pack)
-  int32_t* fwd_phase_off = nullptr;  // [tasks][phases + 1] edge offsets per window
-  int32_t* fwd_perm = nullptr;   // CSR edge id of each permuted forward edge
-  uint2* fwd_cv = nullptr;       // {column | (row within the task << kFwdColBits), val bits}
+  maxk::DeviceBuf<int32_t> fwd_phase_off;  // [tasks][phases + 1] edge offsets per window
+  maxk::DeviceBuf<int32_t> fwd_perm;  // CSR edge id of each permuted forward edge
+  maxk::DeviceBuf<uint2> fwd_cv;  // {column | (row within the task << kFwdColBits), val bits}
   int32_t n_fwd_tasks = 0;
-  int32_t* zero_rows = nullptr;  // rows written by split tasks (atomic), zeroed first
+  maxk::DeviceBuf<int32_t> zero_rows;  // rows written by split tasks (atomic), zeroed first
   int32_t n_zero_rows = 0;
   // ---- backward, column blocks (sspmm_bwd4_kernel): one 12-B record per reordered edge
   // {row * D * 4 (or the row index when grad_out exceeds 4 GiB), column within its block,
@@ -226,20 +227,20 @@ struct maxk_plan {
   int32_t bwd_big = 0;           // grad_out > 4 GiB: 64-bit row addressing
   int32_t bwd_block_cols = 0;
   int32_t n_bwd_blocks = 0;
-  maxk::BwdTask* bwd_tasks = nullptr;
+  maxk::DeviceBuf<maxk::BwdTask> bwd_tasks;
   int32_t n_bwd_tasks = 0;
   int32_t n_bwd_shared = 0;
-  int32_t* bwd_perm = nullptr;   // CSR edge id of each reordered edge
-  uint32_t* bwd_rec = nullptr;   // [num_edges + kBwdRecPad][3]
-  uint32_t* bwd_sel = nullptr;   // plan-owned workspace: the slabs (bwd_slab_floats)
+  maxk::DeviceBuf<int32_t> bwd_perm;  // CSR edge id of each reordered edge
+  maxk::DeviceBuf<uint32_t> bwd_rec;  // [num_edges + kBwdRecPad][3]
+  maxk::DeviceBuf<uint32_t> bwd_sel;  // plan-owned workspace: the slabs (bwd_slab_floats)
   // two-pass backward (low row reuse): a row pass writes each edge's k products val *
   // grad_out[r, sel(c)] into the edge's slot of bwd_tbuf (CSR order), a column pass sums the
   // slots of each column's in-edges (bwd_perm, bwd_colptr)
   int32_t bwd_twopass = 0;
   int32_t bwd_tp_rows = 1;       // R: destination rows per wavefront of the row pass
-  uint32_t* bwd_erec = nullptr;  // [num_edges][2] CSR order: {column | (row % R) << 26, val}
-  float* bwd_tbuf = nullptr;     // [max chunk edges][k] plan-owned workspace
-  int32_t* bwd_colptr = nullptr; // [num_cols + 1] offsets of the column-sorted edges
+  maxk::DeviceBuf<uint32_t> bwd_erec;  // [num_edges][2] CSR order: {column | (row % R) << 26, val}
+  maxk::DeviceBuf<float> bwd_tbuf;  // [max chunk edges][k] plan-owned workspace
+  maxk::DeviceBuf<int32_t> bwd_colptr;  // [num_cols + 1] offsets of the column-sorted edges
   // row chunks of the two-pass backward (workspace bounded by kBwdTwoPassWorkspaceCap):
   // chunk p covers destination rows [tp_rows[p], tp_rows[p+1]) = CSR edges [tp_edges[p],
   // tp_edges[p+1]); bwd_colptr2[p * NC + c] = first column-sorted position of column c whose
@@ -247,11 +248,11 @@ struct maxk_plan {
   int32_t bwd_tp_chunks = 1;
   std::vector<int32_t> tp_rows;
   std::vector<int64_t> tp_edges;
-  int32_t* bwd_colptr2 = nullptr;
+  maxk::DeviceBuf<int32_t> bwd_colptr2;
   // column order of the column blocks (maxk_plan_options.col_order): bwd_corder[p] = the
   // source column placed at position p of the blocks (nullptr: identity)
   int32_t col_order = 1;
-  int32_t* bwd_corder = nullptr;
+  maxk::DeviceBuf<int32_t> bwd_corder;
   // slab flush of split blocks: piece 0 of a block stores into grad_sp, piece p > 0 into its
   // [C][k] slab region (bwd_slab_floats f32 in all, at byte bwd_slab_off of the backward
   // workspace, behind the selector words); bwd_combine_kernel adds each block's regions in
@@ -259,7 +260,7 @@ struct maxk_plan {
   // more than one piece. bwd_slab_floats == 0 with split blocks: global float atomics
   int64_t bwd_slab_floats = 0;
   int64_t bwd_slab_off = 0;
-  int4* bwd_combine = nullptr;
+  maxk::DeviceBuf<int4> bwd_combine;
   int32_t n_bwd_combine = 0;
   int64_t device_bytes = 0;
   // per-call scratch: the forward's packed CBSR records and statistics words, the backward's

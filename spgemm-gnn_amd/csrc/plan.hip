@@ -23,9 +23,9 @@
 #include <cmath>
 #include <cstddef>
 #include <cstring>
+#include <memory>
+#include <utility>
 #include <vector>
-
-#include <cstdlib>
 
 #include "common.h"
 
@@ -342,62 +342,60 @@ __global__ void iota_kernel(int n, int32_t* __restrict__ out) {
   if (i < n) out[i] = i;
 }
 
-static void dfree(void* q) { if (q) (void)hipFree(q); }
-
-// The large streamed plan arrays (forward edge words, backward records). MAXK_PLAN_MALLOC=
-// contiguous asks the runtime for physically contiguous memory (hipDeviceMallocContiguous),
-// falling back to hipMalloc when it cannot (round 6 experiment on allocation-dependent kernel
-// times).
-static hipError_t plan_malloc(void** q, size_t bytes) {
-  static const int mode = [] {
-    const char* e = std::getenv("MAXK_PLAN_MALLOC");
-    return (e && std::string(e) == "contiguous") ? 1 : 0;
-  }();
-  if (mode == 1 && hipExtMallocWithFlags(q, bytes, hipDeviceMallocContiguous) == hipSuccess)
-    return hipSuccess;
-  (void)hipGetLastError();
-  return hipMalloc(q, bytes);
-}
-template <class T>
-static hipError_t plan_malloc(T** q, size_t bytes) {
-  return plan_malloc(reinterpret_cast<void**>(q), bytes);
-}
-
 static int grid_for(int64_t n, int threads) {
   int64_t g = (n + threads - 1) / threads;
   return (int)std::max<int64_t>(1, std::min<int64_t>(g, 65536));
 }
 
-static void free_plan(maxk_plan* p) {
-  if (!p) return;
-  dfree(p->fwd_tasks);
-  dfree(p->fwd_rec);
-  dfree(p->fwd_perm);
-  dfree(p->fwd_cv);
-  dfree(p->fwd_fix);
-  dfree(p->fwd_rowptr);
-  dfree(p->fwd_phase_off);
-  dfree(p->zero_rows);
-  dfree(p->bwd_tasks);
-  dfree(p->bwd_perm);
-  dfree(p->bwd_rec);
-  dfree(p->bwd_sel);
-  dfree(p->bwd_colptr);
-  dfree(p->bwd_erec);
-  dfree(p->bwd_tbuf);
-  dfree(p->bwd_combine);
-  dfree(p->bwd_colptr2);
-  dfree(p->bwd_corder);
-  delete p;
+// Every array the plan owns is taken (or, a scratch buffer promoted into the plan, moved in)
+// through these two, so device_bytes is the sum of the plan's own allocations at their
+// requested sizes: the workspaces fwd_rec, bwd_sel and bwd_tbuf count exactly when the plan
+// allocates them.
+template <class T>
+static hipError_t plan_alloc(maxk_plan* p, DeviceBuf<T>& a, size_t count, bool streamed = false) {
+  const hipError_t e = a.alloc(count, streamed);
+  if (e == hipSuccess) p->device_bytes += (int64_t)a.bytes();
+  return e;
+}
+template <class T>
+static void plan_adopt(maxk_plan* p, DeviceBuf<T>& a, DeviceBuf<T>&& scratch) {
+  a = std::move(scratch);
+  p->device_bytes += (int64_t)a.bytes();
 }
 
-// Column order of the column blocks (col_order 2 scattered, 4 the caller's): *order = device
+// Host vector -> device buffer on the stream. The copy is asynchronous: `v` must outlive it, so
+// it either lives in the build context (which outlives the build's last synchronise) or the
+// stage that owns it synchronises the stream before it returns.
+template <class T>
+static hipError_t upload(const DeviceBuf<T>& dst, const std::vector<T>& v, hipStream_t s) {
+  return hipMemcpyAsync(dst, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, s);
+}
+
+// The one radix sort of (key, CSR edge id) pairs by key bits [0, end_bit): hipcub's size query,
+// its temporary, the sort. `temp` is freed before the new one is taken, so a second sort never
+// holds two.
+template <class K>
+static hipError_t sort_pairs(DeviceBuf<char>& temp, const DeviceBuf<K>& keys_in,
+                             const DeviceBuf<K>& keys_out, const int32_t* ids_in, int32_t* ids_out,
+                             int64_t n, int end_bit, hipStream_t s) {
+  temp.reset();
+  size_t bytes = 0;
+  auto sort = [&] {  // with no temporary: the size query
+    return hipcub::DeviceRadixSort::SortPairs(temp.get(), bytes, keys_in.get(), keys_out.get(),
+                                              ids_in, ids_out, (int)n, 0, end_bit, s);
+  };
+  hipError_t e = sort();
+  if (e == hipSuccess) e = temp.alloc(bytes);
+  return e == hipSuccess ? sort() : e;
+}
+
+// Column order of the column blocks (col_order 2 scattered, 4 the caller's): order = device
 // int32 [NC], order[p] = column at position p. The caller's order must be a permutation of
 // [0, NC): *bad is set otherwise, and nothing is scattered with it.
 static hipError_t build_col_order(int mode, int NC, const int32_t* user, hipStream_t s,
-                                  int32_t** order, bool* bad) {
+                                  DeviceBuf<int32_t>& order, bool* bad) {
   *bad = false;
-  hipError_t e = hipMalloc(order, sizeof(int32_t) * (size_t)NC);
+  hipError_t e = order.alloc((size_t)NC);
   if (e != hipSuccess) return e;
   if (mode == 4) {
     std::vector<int32_t> ho(NC);
@@ -411,14 +409,15 @@ static hipError_t build_col_order(int mode, int NC, const int32_t* user, hipStre
       if (!*bad) seen[c] = 1;
     }
     if (*bad) return hipSuccess;
-    return hipMemcpyAsync(*order, ho.data(), sizeof(int32_t) * NC, hipMemcpyHostToDevice, s);
+    e = upload(order, ho, s);
+    return e == hipSuccess ? hipStreamSynchronize(s) : e;  // ho ends here
   }
   // a ~ 0.618 NC, coprime with NC (b: a fixed offset)
   int64_t a = std::max<int64_t>(1, (int64_t)(0.6180339887 * NC));
   auto gcd = [](int64_t x, int64_t y) { while (y) { const int64_t t = x % y; x = y; y = t; } return x; };
   while (gcd(a, NC) != 1) ++a;
   hipLaunchKernelGGL(affine_order_kernel, dim3((NC + 255) / 256), dim3(256), 0, s, NC, a % NC,
-                     (int64_t)(NC / 3), *order);
+                     (int64_t)(NC / 3), order);
   return hipGetLastError();
 }
 
@@ -619,11 +618,65 @@ static int device_cus() {
   return 256;
 }
 
-static int plan_create_impl(const int32_t* ptr, const int32_t* idx, const float* val, int32_t N,
-                            int32_t NC, int64_t E, int32_t D, int32_t k,
-                            const maxk_plan_options& o, const int32_t* user_order, void* stream,
-                            maxk_plan** out_plan) {
-  *out_plan = nullptr;
+namespace {
+
+// A plan build: the inputs, the plan under construction and what more than one stage needs.
+// Each stage below is a function of it that returns a library code; a stage's own scratch is a
+// local DeviceBuf and dies at the stage's return, on success and on every error alike.
+struct PlanBuild {
+  const int32_t* ptr;
+  const int32_t* idx;
+  const float* val;
+  int32_t N, NC;
+  int64_t E;
+  int32_t D, k;
+  const maxk_plan_options& o;
+  const int32_t* user_order;
+  hipStream_t s;
+  std::vector<int32_t> hp;  // host copy of ptr
+  std::unique_ptr<maxk_plan> plan;
+  // ---- decisions
+  bool big_table = false;  // CBSR table past the packed-record thresholds
+  int C = 1, S = 1;        // columns per column block, slot groups
+  int order_mode = 1;
+  bool twopass = false;
+  bool row_hash_ok = false, row_hash = false;  // scattered row order: possible, taken
+  int64_t ra = 1, rb = 0;
+  int rbits = 1;
+  int nblocks = 0;
+  const int32_t* bcolpos = nullptr;  // colpos when the column blocks use the column order
+  // ---- host arrays: the sources of uploads live here, so they outlive their copies
+  std::vector<FwdTask> ftasks;
+  std::vector<int32_t> zrows;
+  std::vector<int64_t> offs;  // first sorted edge of each column block
+  std::vector<BwdTask> btasks;
+  int nshared = 0;
+  // ---- device scratch shared between stages, freed with the context
+  DeviceBuf<int32_t> row_of;   // destination row of each CSR edge (forward sort .. records)
+  DeviceBuf<int32_t> order;    // column order: position -> column (col_order 2, 4)
+  DeviceBuf<int32_t> colpos;   // column -> position
+  DeviceBuf<uint32_t> bkeys;   // block id of each sorted edge (block sort .. block offsets)
+  DeviceBuf<int32_t> brow;     // destination row / block position of each reordered edge
+  DeviceBuf<int32_t> bcol;     // (column blocks: edge gather .. records)
+};
+
+}  // namespace
+
+static int hip_fail(const char* what, hipError_t e) {
+  set_error(std::string("maxk_plan_create: ") + what + ": " + hipGetErrorString(e));
+  return (int)e;
+}
+#define PLAN_TRY(expr)                                         \
+  do {                                                         \
+    const hipError_t _e = (expr);                              \
+    if (_e != hipSuccess) return hip_fail(#expr, _e);          \
+  } while (0)
+
+static int check_args(const PlanBuild& ctx) {
+  const maxk_plan_options& o = ctx.o;
+  const int32_t N = ctx.N, NC = ctx.NC, D = ctx.D, k = ctx.k;
+  const int64_t E = ctx.E;
+  const int32_t *ptr = ctx.ptr, *idx = ctx.idx, *user_order = ctx.user_order;
   if (const int rc = check_options(o)) return rc;
   MAXK_CHECK_ARG(o.col_order != 4 || user_order != nullptr || NC == 0,
                  "maxk_plan_create: col_order 4 needs the col_order argument");
@@ -637,18 +690,14 @@ static int plan_create_impl(const int32_t* ptr, const int32_t* idx, const float*
   MAXK_CHECK_ARG(D >= 1 && D <= kMaxDim, "maxk_plan_create: dim_origin must be in [1, 256]");
   MAXK_CHECK_ARG(k >= 1 && k <= D, "k must be between 1 and input dimension");
   MAXK_CHECK_ARG(ptr != nullptr && (E == 0 || idx != nullptr), "maxk_plan_create: null pointer");
-  hipStream_t s = (hipStream_t)stream;
+  return MAXK_OK;
+}
 
-  maxk_plan* p = new maxk_plan();
-  p->external_ws = o.external_workspace;
-  p->num_nodes = N;
-  p->num_cols = NC;
-  p->num_edges = E;
-  p->dim_origin = D;
-  p->dim_k = k;
-  p->src_ptr = ptr;
-  p->src_idx = idx;
-  p->cus = device_cus();
+// Forward kernel shape: host only, a function of the sizes, the options and the CU count.
+static void choose_fwd_shape(PlanBuild& ctx) {
+  maxk_plan* p = ctx.plan.get();
+  const maxk_plan_options& o = ctx.o;
+  const int32_t N = ctx.N, NC = ctx.NC, D = ctx.D, k = ctx.k;
   const int cus = p->cus;
   // Forward tile rows: 32, or, where a CU's LDS holds only two 32-row accumulators anyway
   // (D >= 213), as many rows as still fit two work-groups (39 at D = 256): more rows share
@@ -696,15 +745,21 @@ static int plan_create_impl(const int32_t* ptr, const int32_t* idx, const float*
   // k = 64 2.22 / 3.37. Not by default at k < 16 (Reddit k = 8 0.93 / 0.91, the stats pass
   // included) or on tables past the packed-record thresholds, whose gathers are HBM-bound
   // (ogbn-products k = 16 3.14 / 3.02, k = 32 4.86 / 4.78).
-  const bool big_table = (double)std::max(NC, 1) * 5.0 * k >
-                         (k >= 32 ? kFwdPackedTableBytes : kFwdPackedTableBytes16);
-  p->fwd_fixed = (o.fwd_fixed == 1 || (o.fwd_fixed == 0 && k >= 16 && !big_table)) &&
+  ctx.big_table = (double)std::max(NC, 1) * 5.0 * k >
+                (k >= 32 ? kFwdPackedTableBytes : kFwdPackedTableBytes16);
+  p->fwd_fixed = (o.fwd_fixed == 1 || (o.fwd_fixed == 0 && k >= 16 && !ctx.big_table)) &&
                  (k % 4 == 0 || p->fwd_chunk3 || p->fwd_chunk2);
   // forward quad-shared edge-word loads with the fixed-point kernel (k = 16 1.19 -> 1.16 ms,
   // k = 32 1.81 -> 1.78); neutral-to-slower on the f64 kernel
   p->fwd_quad = p->fwd_fixed;
+}
 
-  // ---- backward kernel shape (column blocks)
+// Backward kernel shape (column blocks): host only, as the forward's.
+static void choose_bwd_shape(PlanBuild& ctx) {
+  maxk_plan* p = ctx.plan.get();
+  const maxk_plan_options& o = ctx.o;
+  const int32_t N = ctx.N, NC = ctx.NC, D = ctx.D, k = ctx.k;
+  const int64_t E = ctx.E;
   const int lds_budget = o.bwd_lds_bytes ? o.bwd_lds_bytes : kBwdLdsBudget;
   // k = 8: two slots per lane, so a gather instruction covers 16 edges (4 lanes per edge)
   // instead of 32, when a column block sees few edges per grad_out row (32 edges then span
@@ -756,164 +811,151 @@ static int plan_create_impl(const int32_t* ptr, const int32_t* idx, const float*
   // bytes of LDS per column: ks f32 accumulators + ks staged selector bytes
   int C = std::max(1, (lds_budget - 16) / (5 * p->bwd_ks));
   C = std::min(C, std::max(NC, 1));
+  ctx.C = C;
+  ctx.S = S;
+}
 
-  int32_t* row_of = nullptr;
-  uint32_t* keys_in = nullptr;
-  uint32_t* keys_out = nullptr;
-  int32_t* ids_in = nullptr;
-  int32_t* brow = nullptr;   // destination row / block position of each reordered edge
-  int32_t* bcol = nullptr;
-  void* temp = nullptr;
-  int32_t* d_offs = nullptr;
-  int* d_bad = nullptr;
-  int32_t* order = nullptr;   // column order: position -> column (col_order 2, 4)
-  int32_t* colpos = nullptr;  // column -> position
-  auto fail = [&](int rc) {
-    dfree(order); dfree(colpos); dfree(row_of); dfree(keys_in); dfree(keys_out); dfree(ids_in);
-    dfree(brow); dfree(bcol); dfree(temp); dfree(d_offs); dfree(d_bad);
-    free_plan(p);
-    return rc;
-  };
-#define PLAN_TRY(expr)                                                            \
-  do {                                                                            \
-    hipError_t _e = (expr);                                                       \
-    if (_e != hipSuccess) {                                                       \
-      set_error(std::string("maxk_plan_create: ") + #expr + ": " + hipGetErrorString(_e)); \
-      return fail((int)_e);                                                       \
-    }                                                                             \
-  } while (0)
-  auto need_row_of = [&]() -> hipError_t {
-    if (row_of || E == 0) return hipSuccess;
-    hipError_t e = hipMalloc(&row_of, sizeof(int32_t) * E);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(expand_rows_kernel, dim3((N + 3) / 4), dim3(256), 0, s, ptr, N, row_of);
-    return hipGetLastError();
-  };
+// row_of: taken by the first stage that needs it (the forward sort, else the block sort).
+static hipError_t need_row_of(PlanBuild& ctx) {
+  if (ctx.row_of || ctx.E == 0) return hipSuccess;
+  const hipError_t e = ctx.row_of.alloc((size_t)ctx.E);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(expand_rows_kernel, dim3((ctx.N + 3) / 4), dim3(256), 0, ctx.s, ctx.ptr,
+                     ctx.N, ctx.row_of);
+  return hipGetLastError();
+}
 
-  // ---------------- forward
-  std::vector<int32_t> hp(N + 1);
-  PLAN_TRY(hipMemcpyAsync(hp.data(), ptr, sizeof(int32_t) * (N + 1), hipMemcpyDeviceToHost, s));
-  PLAN_TRY(hipStreamSynchronize(s));
-  if (hp[0] != 0 || (int64_t)hp[N] != E) {
-    set_error("maxk_plan_create: ptr[0] must be 0 and ptr[N] must equal num_edges");
-    return fail(MAXK_ERR_INVALID_ARG);
-  }
-  for (int r = 0; r < N; ++r) {
-    if (hp[r + 1] < hp[r]) {
-      set_error("maxk_plan_create: ptr must be non-decreasing");
-      return fail(MAXK_ERR_INVALID_ARG);
-    }
-  }
+// Host copy of ptr, validated before anything is derived from it.
+static int read_ptr(PlanBuild& ctx) {
+  const int32_t N = ctx.N;
+  std::vector<int32_t>& hp = ctx.hp;
+  hp.resize(N + 1);
+  PLAN_TRY(hipMemcpyAsync(hp.data(), ctx.ptr, sizeof(int32_t) * (N + 1), hipMemcpyDeviceToHost,
+                          ctx.s));
+  PLAN_TRY(hipStreamSynchronize(ctx.s));
+  MAXK_CHECK_ARG(hp[0] == 0 && (int64_t)hp[N] == ctx.E,
+                 "maxk_plan_create: ptr[0] must be 0 and ptr[N] must equal num_edges");
+  for (int r = 0; r < N; ++r)
+    MAXK_CHECK_ARG(hp[r + 1] >= hp[r], "maxk_plan_create: ptr must be non-decreasing");
+  return MAXK_OK;
+}
+
+static int build_column_order(PlanBuild& ctx) {
+  const int32_t NC = ctx.NC;
   // ---------------- column order (col_order 2 scattered, 4 the caller's): the column blocks
   // take position ranges of it. The forward keeps its column-sorted sweep (sweeping in a
   // clustered order measured much slower: k = 16 1.07 -> 1.36 ms, k = 32 1.61 -> 2.75)
-  const int order_mode = o.col_order == 0 ? 1 : o.col_order;
-  if (order_mode >= 2 && NC > 0) {
+  ctx.order_mode = ctx.o.col_order == 0 ? 1 : ctx.o.col_order;
+  if (ctx.order_mode >= 2 && NC > 0) {
     bool bad_order = false;
-    PLAN_TRY(build_col_order(order_mode, NC, user_order, s, &order, &bad_order));
-    if (bad_order) {
-      set_error("maxk_plan_create: col_order is not a permutation of [0, num_cols)");
-      return fail(MAXK_ERR_INVALID_ARG);
-    }
-    PLAN_TRY(hipMalloc(&colpos, sizeof(int32_t) * NC));
-    hipLaunchKernelGGL(invert_order_kernel, dim3((NC + 255) / 256), dim3(256), 0, s, order, NC, colpos);
+    PLAN_TRY(build_col_order(ctx.order_mode, NC, ctx.user_order, ctx.s, ctx.order, &bad_order));
+    MAXK_CHECK_ARG(!bad_order, "maxk_plan_create: col_order is not a permutation of [0, num_cols)");
+    PLAN_TRY(ctx.colpos.alloc((size_t)NC));
+    hipLaunchKernelGGL(invert_order_kernel, dim3((NC + 255) / 256), dim3(256), 0, ctx.s, ctx.order,
+                       NC, ctx.colpos);
     PLAN_TRY(hipGetLastError());
   }
+  return MAXK_OK;
+}
 
-  std::vector<FwdTask> ftasks;
-  std::vector<int32_t> zrows;
-  build_fwd_tasks(hp, N, p->fwd_tile_rows, o.fwd_task_cap, ftasks, zrows);
+// The forward's permuted edge order and edge words: fwd_perm, fwd_cv, and the tasks' new
+// contiguous edge ranges. Scratch: the three task tables, rl, ids, the 64-bit key pair and
+// hipcub's temporary, E * (4 + 4 + 8 + 8) bytes and hipcub's, all released at return, before
+// the backward takes its own; row_of is the one survivor. The final synchronise is what lets
+// them (and the host tables) go.
+static int sort_fwd_edges(PlanBuild& ctx) {
+  maxk_plan* p = ctx.plan.get();
+  std::vector<FwdTask>& ftasks = ctx.ftasks;
+  const int32_t NC = ctx.NC;
+  const int64_t E = ctx.E;
+  hipStream_t s = ctx.s;
+  // permuted edge order (see fwd_key_kernel): tasks keep their CSR edge sets
+  const int nt = (int)ftasks.size();
+  std::vector<int32_t> torder(nt);
+  for (int i = 0; i < nt; ++i) torder[i] = i;
+  // by first edge, and among equal first edges the empty tasks (an edgeless tile shares its
+  // e0 with the next tile) before the one task that owns edges there: fwd_key_kernel takes
+  // the LAST task whose first edge is <= e (an edgeless tile ordered last took the next
+  // tile's edges, whose rows then stayed zero: tests/test_gpu_fuzz.py)
+  std::sort(torder.begin(), torder.end(), [&](int a, int b) {
+    if (ftasks[a].e0 != ftasks[b].e0) return ftasks[a].e0 < ftasks[b].e0;
+    return ftasks[a].e1 < ftasks[b].e1;
+  });
+  std::vector<int32_t> starts(nt), ranks(nt), row0s(nt);
+  for (int i = 0; i < nt; ++i) {
+    starts[i] = ftasks[torder[i]].e0;
+    ranks[i] = torder[i];
+    row0s[i] = ftasks[torder[i]].row0;
+  }
+  int32_t pos = 0;
+  for (int i = 0; i < nt; ++i) {  // new contiguous ranges, launch order
+    const int32_t len = ftasks[i].e1 - ftasks[i].e0;
+    ftasks[i].e0 = pos;
+    ftasks[i].e1 = pos + len;
+    pos += len;
+  }
+  if (E > 0) {
+    int cbits = 1;
+    while ((1ll << cbits) < (long long)NC) ++cbits;
+    int tbits = 1;
+    while ((1ll << tbits) < (long long)nt) ++tbits;
+    DeviceBuf<int32_t> d_starts, d_ranks, d_row0s, d_rl, d_ids;
+    DeviceBuf<uint64_t> d_kin, d_kout;
+    DeviceBuf<char> d_tmp;
+    PLAN_TRY(need_row_of(ctx));
+    PLAN_TRY(d_starts.alloc(nt));
+    PLAN_TRY(d_ranks.alloc(nt));
+    PLAN_TRY(d_row0s.alloc(nt));
+    PLAN_TRY(upload(d_starts, starts, s));
+    PLAN_TRY(upload(d_ranks, ranks, s));
+    PLAN_TRY(upload(d_row0s, row0s, s));
+    PLAN_TRY(d_rl.alloc((size_t)E));
+    PLAN_TRY(d_ids.alloc((size_t)E));
+    PLAN_TRY(d_kin.alloc((size_t)E));
+    PLAN_TRY(d_kout.alloc((size_t)E));
+    PLAN_TRY(plan_alloc(p, p->fwd_perm, (size_t)E));
+    hipLaunchKernelGGL(fwd_key_kernel, dim3(grid_for(E, 256)), dim3(256), 0, s, ctx.idx, ctx.row_of,
+                       E, d_starts, d_ranks, d_row0s, nt, cbits, d_kin, d_ids, d_rl);
+    PLAN_TRY(hipGetLastError());
+    PLAN_TRY(sort_pairs(d_tmp, d_kin, d_kout, d_ids, p->fwd_perm, E, cbits + tbits, s));
+    // one word past the end, zero (column 0, row 0, value 0): the forward's 16-B edge-word
+    // loads read edges in pairs from an even index, and a masked lane still gathers the
+    // record of the column it read
+    PLAN_TRY(plan_alloc(p, p->fwd_cv, (size_t)E + 1, true));
+    PLAN_TRY(hipMemsetAsync(p->fwd_cv + E, 0, sizeof(uint2), s));
+    hipLaunchKernelGGL(gather_fwd_kernel, dim3(grid_for(E, 256)), dim3(256), 0, s,
+                       p->fwd_perm, ctx.idx, d_rl, ctx.val, E, p->fwd_cv, true);
+    PLAN_TRY(hipGetLastError());
+    PLAN_TRY(hipStreamSynchronize(s));
+  }
+  return MAXK_OK;
+}
+
+// Forward build: tasks, permuted sort and edge words, fixed-point bounds, column windows, zero
+// rows.
+static int build_forward(PlanBuild& ctx) {
+  maxk_plan* p = ctx.plan.get();
+  const maxk_plan_options& o = ctx.o;
+  std::vector<FwdTask>& ftasks = ctx.ftasks;
+  std::vector<int32_t>& zrows = ctx.zrows;
+  const int32_t N = ctx.N, NC = ctx.NC, k = ctx.k;
+  const int64_t E = ctx.E;
+  hipStream_t s = ctx.s;
+  build_fwd_tasks(ctx.hp, N, p->fwd_tile_rows, o.fwd_task_cap, ftasks, zrows);
   p->n_fwd_tasks = (int32_t)ftasks.size();
   p->n_zero_rows = (int32_t)zrows.size();
   if (!ftasks.empty()) {
-    // permuted edge order (see fwd_key_kernel): tasks keep their CSR edge sets
     const int nt = (int)ftasks.size();
-    std::vector<int32_t> torder(nt);
-    for (int i = 0; i < nt; ++i) torder[i] = i;
-    // by first edge, and among equal first edges the empty tasks (an edgeless tile shares its
-    // e0 with the next tile) before the one task that owns edges there: fwd_key_kernel takes
-    // the LAST task whose first edge is <= e (an edgeless tile ordered last took the next
-    // tile's edges, whose rows then stayed zero: tests/test_gpu_fuzz.py)
-    std::sort(torder.begin(), torder.end(), [&](int a, int b) {
-      if (ftasks[a].e0 != ftasks[b].e0) return ftasks[a].e0 < ftasks[b].e0;
-      return ftasks[a].e1 < ftasks[b].e1;
-    });
-    std::vector<int32_t> starts(nt), ranks(nt), row0s(nt);
-    for (int i = 0; i < nt; ++i) {
-      starts[i] = ftasks[torder[i]].e0;
-      ranks[i] = torder[i];
-      row0s[i] = ftasks[torder[i]].row0;
-    }
-    int32_t pos = 0;
-    for (int i = 0; i < nt; ++i) {  // new contiguous ranges, launch order
-      const int32_t len = ftasks[i].e1 - ftasks[i].e0;
-      ftasks[i].e0 = pos;
-      ftasks[i].e1 = pos + len;
-      pos += len;
-    }
-    if (E > 0) {
-      int cbits = 1;
-      while ((1ll << cbits) < (long long)NC) ++cbits;
-      int tbits = 1;
-      while ((1ll << tbits) < (long long)nt) ++tbits;
-      int32_t *d_starts = nullptr, *d_ranks = nullptr, *d_row0s = nullptr, *d_rl = nullptr,
-              *d_ids = nullptr;
-      uint64_t *d_kin = nullptr, *d_kout = nullptr;
-      void* d_tmp = nullptr;
-      const hipError_t fe = [&]() -> hipError_t {
-        hipError_t e = need_row_of();
-        if (e == hipSuccess) e = hipMalloc(&d_starts, sizeof(int32_t) * nt);
-        if (e == hipSuccess) e = hipMalloc(&d_ranks, sizeof(int32_t) * nt);
-        if (e == hipSuccess) e = hipMalloc(&d_row0s, sizeof(int32_t) * nt);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_starts, starts.data(), sizeof(int32_t) * nt, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_ranks, ranks.data(), sizeof(int32_t) * nt, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_row0s, row0s.data(), sizeof(int32_t) * nt, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMalloc(&d_rl, sizeof(int32_t) * E);
-        if (e == hipSuccess) e = hipMalloc(&d_ids, sizeof(int32_t) * E);
-        if (e == hipSuccess) e = hipMalloc(&d_kin, sizeof(uint64_t) * E);
-        if (e == hipSuccess) e = hipMalloc(&d_kout, sizeof(uint64_t) * E);
-        if (e == hipSuccess) e = hipMalloc(&p->fwd_perm, sizeof(int32_t) * E);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(fwd_key_kernel, dim3(grid_for(E, 256)), dim3(256), 0, s, idx, row_of, E,
-                           d_starts, d_ranks, d_row0s, nt, cbits, d_kin, d_ids, d_rl);
-        e = hipGetLastError();
-        size_t tb = 0;
-        if (e == hipSuccess)
-          e = hipcub::DeviceRadixSort::SortPairs(nullptr, tb, d_kin, d_kout, d_ids, p->fwd_perm,
-                                                 (int)E, 0, cbits + tbits, s);
-        if (e == hipSuccess) e = hipMalloc(&d_tmp, tb);
-        if (e == hipSuccess)
-          e = hipcub::DeviceRadixSort::SortPairs(d_tmp, tb, d_kin, d_kout, d_ids, p->fwd_perm,
-                                                 (int)E, 0, cbits + tbits, s);
-        // one word past the end, zero (column 0, row 0, value 0): the forward's 16-B edge-word
-        // loads read edges in pairs from an even index, and a masked lane still gathers the
-        // record of the column it read
-        if (e == hipSuccess) e = plan_malloc(&p->fwd_cv, sizeof(uint2) * (E + 1));
-        if (e == hipSuccess) e = hipMemsetAsync(p->fwd_cv + E, 0, sizeof(uint2), s);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(gather_fwd_kernel, dim3(grid_for(E, 256)), dim3(256), 0, s, p->fwd_perm,
-                           idx, d_rl, val, E, p->fwd_cv, true);
-        e = hipGetLastError();
-        return e == hipSuccess ? hipStreamSynchronize(s) : e;
-      }();
-      dfree(d_starts); dfree(d_ranks); dfree(d_row0s); dfree(d_rl); dfree(d_ids);
-      dfree(d_kin); dfree(d_kout); dfree(d_tmp);
-      PLAN_TRY(fe);
-      p->device_bytes += (int64_t)E * 12 + 8;
-    }
-    PLAN_TRY(hipMalloc(&p->fwd_tasks, sizeof(FwdTask) * ftasks.size()));
-    PLAN_TRY(hipMemcpyAsync(p->fwd_tasks, ftasks.data(), sizeof(FwdTask) * ftasks.size(),
-                            hipMemcpyHostToDevice, s));
-    p->device_bytes += sizeof(FwdTask) * ftasks.size();
+    if (const int rc = sort_fwd_edges(ctx)) return rc;
+    PLAN_TRY(plan_alloc(p, p->fwd_tasks, ftasks.size()));
+    PLAN_TRY(upload(p->fwd_tasks, ftasks, s));
     if (p->fwd_fixed) {
-      PLAN_TRY(hipMalloc(&p->fwd_fix, sizeof(int2) * ftasks.size()));
-      p->device_bytes += sizeof(int2) * ftasks.size();
+      PLAN_TRY(plan_alloc(p, p->fwd_fix, ftasks.size()));
       // a copy of ptr: maxk_plan_refresh_values recomputes the bounds without the caller's
-      PLAN_TRY(hipMalloc(&p->fwd_rowptr, sizeof(int32_t) * ((size_t)N + 1)));
-      PLAN_TRY(hipMemcpyAsync(p->fwd_rowptr, ptr, sizeof(int32_t) * ((size_t)N + 1),
+      PLAN_TRY(plan_alloc(p, p->fwd_rowptr, (size_t)N + 1));
+      PLAN_TRY(hipMemcpyAsync(p->fwd_rowptr, ctx.ptr, sizeof(int32_t) * ((size_t)N + 1),
                               hipMemcpyDeviceToDevice, s));
-      p->device_bytes += sizeof(int32_t) * ((int64_t)N + 1);
-      PLAN_TRY(fwd_fix_stats(p, p->fwd_rowptr, val, s));
+      PLAN_TRY(fwd_fix_stats(p, p->fwd_rowptr, ctx.val, s));
     }
     // Column windows: one launch whose tiles start their column-sorted sweep at the window a
     // shared clock points to (fwd_rot_ticks per window, about one tile's duration per full
@@ -939,19 +981,25 @@ static int plan_create_impl(const int32_t* ptr, const int32_t* idx, const float*
     }
     B = std::max(1, std::min(B, std::max(NC, 1)));
     p->fwd_phases = B;
-    PLAN_TRY(hipMalloc(&p->fwd_phase_off, sizeof(int32_t) * nt * (B + 1)));
-    p->device_bytes += sizeof(int32_t) * nt * (B + 1);
+    PLAN_TRY(plan_alloc(p, p->fwd_phase_off, (size_t)nt * (B + 1)));
     hipLaunchKernelGGL(fwd_phase_kernel, dim3((nt * (B + 1) + 255) / 256), dim3(256), 0, s,
                        p->fwd_tasks, nt, p->fwd_cv, NC, B, p->fwd_phase_off);
     PLAN_TRY(hipGetLastError());
   }
   if (!zrows.empty()) {
-    PLAN_TRY(hipMalloc(&p->zero_rows, sizeof(int32_t) * zrows.size()));
-    PLAN_TRY(hipMemcpyAsync(p->zero_rows, zrows.data(), sizeof(int32_t) * zrows.size(),
-                            hipMemcpyHostToDevice, s));
-    p->device_bytes += sizeof(int32_t) * zrows.size();
+    PLAN_TRY(plan_alloc(p, p->zero_rows, zrows.size()));
+    PLAN_TRY(upload(p->zero_rows, zrows, s));
   }
+  return MAXK_OK;
+}
 
+// Which table layout the forward gathers from, and the per-call workspace that goes with it.
+static int layout_fwd_workspace(PlanBuild& ctx) {
+  maxk_plan* p = ctx.plan.get();
+  const maxk_plan_options& o = ctx.o;
+  const int32_t NC = ctx.NC, k = ctx.k;
+  const int64_t E = ctx.E;
+  const bool big_table = ctx.big_table;
   // Two tables (no record pack): Reddit k = 32 2.65 -> 2.53 ms, k = 64 4.98 -> 4.92 (k = 16:
   // 1.35 vs 1.39 packed); and where the per-call pack of all NC records costs more than it
   // saves: below kFwdPackMinEdgesPerCol edges per column, or below kFwdPackMinEdgesPerColL2
@@ -986,12 +1034,20 @@ static int plan_create_impl(const int32_t* ptr, const int32_t* idx, const float*
     p->fwd_xstat_off = (p->fwd_ws_bytes + 255) / 256 * 256;
     p->fwd_ws_bytes = p->fwd_xstat_off + 256;
   }
-  if (p->fwd_ws_bytes > 0 && !p->external_ws) {  // plan-owned per-call pack buffer
-    PLAN_TRY(hipMalloc(&p->fwd_rec, (size_t)p->fwd_ws_bytes));
-    p->device_bytes += p->fwd_ws_bytes;
-  }
+  if (p->fwd_ws_bytes > 0 && !p->external_ws)  // plan-owned per-call pack buffer
+    PLAN_TRY(plan_alloc(p, p->fwd_rec, (size_t)p->fwd_ws_bytes));
+  return MAXK_OK;
+}
 
-  // ---------------- backward
+// Two-pass or column blocks, the row-hash parameters and the block count: host only (the
+// automatic choice asks the device for its free memory).
+static void choose_bwd_algo(PlanBuild& ctx) {
+  maxk_plan* p = ctx.plan.get();
+  const maxk_plan_options& o = ctx.o;
+  const std::vector<int32_t>& hp = ctx.hp;
+  const int32_t N = ctx.N, NC = ctx.NC, k = ctx.k;
+  const int64_t E = ctx.E;
+  int C = ctx.C;
   // Two-pass backward (bwd_algo = 3; auto when a column block would see each grad_out row it
   // fetches about once): a row pass stages grad_out[r] in LDS once per row and writes each
   // edge's k products into its slot of an E x k workspace (CSR order), then a column pass
@@ -1020,22 +1076,20 @@ static int plan_create_impl(const int32_t* ptr, const int32_t* idx, const float*
   p->bwd_twopass = twopass;
   p->bwd_tp_rows = R;
   if (twopass) C = 1;
+  ctx.twopass = twopass;
   // the column order applies to the column blocks (the two-pass sorts by the column itself)
-  const int32_t* bcolpos = twopass ? nullptr : colpos;
+  ctx.bcolpos = twopass ? nullptr : ctx.colpos.get();
   // row order inside the blocks' streams: scattered by an affine bijection ra * row + rb mod N
-  const bool row_hash_ok = !twopass && E > 0 && N > 1;
-  bool row_hash = row_hash_ok && o.bwd_row_order == 2;
-  int64_t ra = 1, rb = 0;
-  int rbits = 1;
-  if (row_hash_ok) {
+  ctx.row_hash_ok = !twopass && E > 0 && N > 1;
+  ctx.row_hash = ctx.row_hash_ok && o.bwd_row_order == 2;
+  if (ctx.row_hash_ok) {
     auto gcd = [](int64_t x, int64_t y) { while (y) { const int64_t t = x % y; x = y; y = t; } return x; };
-    ra = std::max<int64_t>(1, (int64_t)(0.6180339887 * N));
+    int64_t ra = std::max<int64_t>(1, (int64_t)(0.6180339887 * N));
     while (gcd(ra, N) != 1) ++ra;
-    ra %= N;
-    rb = N / 7;
-    while ((1ll << rbits) < (long long)N) ++rbits;
+    ctx.ra = ra % N;
+    ctx.rb = N / 7;
+    while ((1ll << ctx.rbits) < (long long)N) ++ctx.rbits;
   }
-  auto row_pos = [&](int32_t r) -> int64_t { return row_hash ? (ra * (int64_t)r + rb) % N : r; };
   int nblocks = NC > 0 ? (NC + C - 1) / C : 0;
   if (!twopass && nblocks >= kXcds) {
     // a multiple of the XCD count, so every XCD owns the same number of column blocks; and
@@ -1048,73 +1102,85 @@ static int plan_create_impl(const int32_t* ptr, const int32_t* idx, const float*
   }
   p->bwd_block_cols = C;
   p->n_bwd_blocks = nblocks;
-  std::vector<int64_t> offs(twopass ? 1 : nblocks + 1, 0);
+  ctx.C = C;
+  ctx.nblocks = nblocks;
+  ctx.offs.assign(twopass ? 1 : nblocks + 1, 0);
   p->bwd_row_order = twopass ? 0 : 1;
+}
+
+namespace {
+// The block sort's own scratch: all of it dies when the stage returns.
+struct BlockSortScratch {
+  DeviceBuf<uint32_t> keys_in;
+  DeviceBuf<int32_t> ids_in;
+  DeviceBuf<char> temp;  // hipcub's
+  DeviceBuf<int> bad;    // set by the key kernels on a column id outside [0, NC)
+};
+}  // namespace
+
+// The block-major sort: bkeys = block id of each sorted edge, bwd_perm = its CSR id. hash: by
+// {block, row position} (bwd_row_order 2). A re-sort frees the previous hipcub temporary
+// first, and the hashed sort's 64-bit key pair (16 E bytes) is released at return, before
+// brow / bcol are taken.
+static int sort_blocks(PlanBuild& ctx, BlockSortScratch& w, bool hash) {
+  maxk_plan* p = ctx.plan.get();
+  const int64_t E = ctx.E;
+  hipStream_t s = ctx.s;
+  int end_bit = 1;
+  while ((1ll << end_bit) < (long long)ctx.nblocks) ++end_bit;
+  w.temp.reset();  // before the key pair below is taken
+  if (!hash) {
+    hipLaunchKernelGGL(bwd_key_kernel, dim3(grid_for(E, 256)), dim3(256), 0, s, ctx.idx, E, ctx.C,
+                       ctx.NC, w.keys_in, w.ids_in, w.bad, ctx.bcolpos);
+    PLAN_TRY(hipGetLastError());
+    PLAN_TRY(sort_pairs(w.temp, w.keys_in, ctx.bkeys, w.ids_in, p->bwd_perm, E, end_bit, s));
+    return MAXK_OK;
+  }
+  // 64-bit keys {block, row position}; their block ids then go to bkeys
+  DeviceBuf<uint64_t> k64_in, k64_out;
+  PLAN_TRY(k64_in.alloc((size_t)E));
+  PLAN_TRY(k64_out.alloc((size_t)E));
+  hipLaunchKernelGGL(bwd_key64_kernel, dim3(grid_for(E, 256)), dim3(256), 0, s, ctx.idx, ctx.row_of,
+                     E, ctx.C, ctx.NC, k64_in, w.ids_in, w.bad, ctx.bcolpos, ctx.ra, ctx.rb, ctx.N,
+                     ctx.rbits);
+  PLAN_TRY(hipGetLastError());
+  PLAN_TRY(sort_pairs(w.temp, k64_in, k64_out, w.ids_in, p->bwd_perm, E, end_bit + ctx.rbits, s));
+  hipLaunchKernelGGL(key_block_kernel, dim3(grid_for(E, 256)), dim3(256), 0, s, k64_out, E,
+                     ctx.rbits, ctx.bkeys);
+  PLAN_TRY(hipGetLastError());
+  PLAN_TRY(hipStreamSynchronize(s));  // the key pair is freed at return
+  return MAXK_OK;
+}
+
+// Block sort, the idx validation read-back and the automatic row-order re-sort.
+//
+// Order of validation and indexing: the key kernels validate every column id and clamp the ones
+// they index colpos with; every kernel before the `bad` read-back below uses a column id as a
+// value (sort keys, edge words) or clamped, never as an index. Nothing that indexes with an
+// unclamped id (gather_bwd_kernel reads colpos[idx[e]]) may be launched before it.
+static int sort_bwd_blocks(PlanBuild& ctx) {
+  maxk_plan* p = ctx.plan.get();
+  const maxk_plan_options& o = ctx.o;
+  const int64_t E = ctx.E;
+  hipStream_t s = ctx.s;
   if (E > 0) {
-    PLAN_TRY(need_row_of());
-    PLAN_TRY(hipMalloc(&keys_in, sizeof(uint32_t) * E));
-    PLAN_TRY(hipMalloc(&keys_out, sizeof(uint32_t) * E));
-    PLAN_TRY(hipMalloc(&ids_in, sizeof(int32_t) * E));
-    PLAN_TRY(hipMalloc(&p->bwd_perm, sizeof(int32_t) * E));
-    PLAN_TRY(hipMalloc(&d_bad, sizeof(int)));
-    PLAN_TRY(hipMemsetAsync(d_bad, 0, sizeof(int), s));
-    int end_bit = 1;
-    while ((1ll << end_bit) < (long long)nblocks) ++end_bit;
-    // the block-major sort: keys_out = block id of each sorted edge, bwd_perm = its CSR id
-    auto sort_blocks = [&](bool hash) -> hipError_t {
-      size_t temp_bytes = 0;
-      dfree(temp);
-      temp = nullptr;
-      if (!hash) {
-        hipLaunchKernelGGL(bwd_key_kernel, dim3(grid_for(E, 256)), dim3(256), 0, s, idx, E, C, NC,
-                           keys_in, ids_in, d_bad, bcolpos);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess)
-          e = hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, keys_in, keys_out, ids_in,
-                                                 p->bwd_perm, (int)E, 0, end_bit, s);
-        if (e == hipSuccess) e = hipMalloc(&temp, temp_bytes);
-        if (e != hipSuccess) return e;
-        return hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, keys_in, keys_out, ids_in,
-                                                  p->bwd_perm, (int)E, 0, end_bit, s);
-      }
-      // 64-bit keys {block, row position}; their block ids then go to keys_out
-      uint64_t *k64_in = nullptr, *k64_out = nullptr;
-      const hipError_t ke = [&]() -> hipError_t {
-        hipError_t e = hipMalloc(&k64_in, sizeof(uint64_t) * E);
-        if (e == hipSuccess) e = hipMalloc(&k64_out, sizeof(uint64_t) * E);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(bwd_key64_kernel, dim3(grid_for(E, 256)), dim3(256), 0, s, idx, row_of,
-                           E, C, NC, k64_in, ids_in, d_bad, bcolpos, ra, rb, N, rbits);
-        e = hipGetLastError();
-        if (e == hipSuccess)
-          e = hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, k64_in, k64_out, ids_in,
-                                                 p->bwd_perm, (int)E, 0, end_bit + rbits, s);
-        if (e == hipSuccess) e = hipMalloc(&temp, temp_bytes);
-        if (e == hipSuccess)
-          e = hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, k64_in, k64_out, ids_in,
-                                                 p->bwd_perm, (int)E, 0, end_bit + rbits, s);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(key_block_kernel, dim3(grid_for(E, 256)), dim3(256), 0, s, k64_out, E,
-                           rbits, keys_out);
-        e = hipGetLastError();
-        return e == hipSuccess ? hipStreamSynchronize(s) : e;
-      }();
-      dfree(k64_in);
-      dfree(k64_out);
-      return ke;
-    };
-    PLAN_TRY(sort_blocks(row_hash));
+    BlockSortScratch w;
+    PLAN_TRY(need_row_of(ctx));
+    PLAN_TRY(w.keys_in.alloc((size_t)E));
+    PLAN_TRY(ctx.bkeys.alloc((size_t)E));
+    PLAN_TRY(w.ids_in.alloc((size_t)E));
+    PLAN_TRY(plan_alloc(p, p->bwd_perm, (size_t)E));
+    PLAN_TRY(w.bad.alloc(1));
+    PLAN_TRY(hipMemsetAsync(w.bad, 0, sizeof(int), s));
+    if (const int rc = sort_blocks(ctx, w, ctx.row_hash)) return rc;
     // the key kernel has validated every column id (clamping the ones it indexed with): refuse
     // a bad idx here, before any kernel indexes with an unclamped one (gather_bwd_kernel reads
     // colpos[idx[e]] under a column order)
     int bad = 0;
-    PLAN_TRY(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    PLAN_TRY(hipMemcpyAsync(&bad, w.bad, sizeof(int), hipMemcpyDeviceToHost, s));
     PLAN_TRY(hipStreamSynchronize(s));
-    if (bad) {
-      set_error("maxk_plan_create: idx contains column ids outside [0, num_cols)");
-      return fail(MAXK_ERR_INVALID_ARG);
-    }
-    if (row_hash_ok && o.bwd_row_order == 0) {
+    MAXK_CHECK_ARG(!bad, "maxk_plan_create: idx contains column ids outside [0, num_cols)");
+    if (ctx.row_hash_ok && o.bwd_row_order == 0) {
       // auto: scatter the rows when the ascending-row streams are mostly dense runs, i.e. many
       // consecutive rows with many edges into the same block (an ID-ordered community: Reddit
       // size, 41 communities, k = 16: 2.31 -> 1.59 ms; k = 32: 3.62 -> 2.45); with rows that
@@ -1123,264 +1189,296 @@ static int plan_create_impl(const int32_t* ptr, const int32_t* idx, const float*
       constexpr int Wn = 2048;
       const int64_t nw = E / Wn;
       if (nw > 0) {
-        int* d_nd = nullptr;
+        DeviceBuf<int> d_nd;
         int nd = 0;
-        const hipError_t de = [&]() -> hipError_t {
-          hipError_t e = hipMalloc(&d_nd, sizeof(int));
-          if (e == hipSuccess) e = hipMemsetAsync(d_nd, 0, sizeof(int), s);
-          if (e != hipSuccess) return e;
-          hipLaunchKernelGGL(dense_window_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s,
-                             keys_out, p->bwd_perm, row_of, E, Wn, d_nd);
-          e = hipGetLastError();
-          if (e == hipSuccess) e = hipMemcpyAsync(&nd, d_nd, sizeof(int), hipMemcpyDeviceToHost, s);
-          return e == hipSuccess ? hipStreamSynchronize(s) : e;
-        }();
-        dfree(d_nd);
-        PLAN_TRY(de);
+        PLAN_TRY(d_nd.alloc(1));
+        PLAN_TRY(hipMemsetAsync(d_nd, 0, sizeof(int), s));
+        hipLaunchKernelGGL(dense_window_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s,
+                           ctx.bkeys, p->bwd_perm, ctx.row_of, E, Wn, d_nd);
+        PLAN_TRY(hipGetLastError());
+        PLAN_TRY(hipMemcpyAsync(&nd, d_nd, sizeof(int), hipMemcpyDeviceToHost, s));
+        PLAN_TRY(hipStreamSynchronize(s));
+        d_nd.reset();
         if (nd > nw / 4) {
-          row_hash = true;
-          PLAN_TRY(sort_blocks(true));
+          ctx.row_hash = true;
+          if (const int rc = sort_blocks(ctx, w, true)) return rc;
         }
       }
     }
-    if (!twopass) p->bwd_row_order = row_hash ? 2 : 1;
-    if (twopass) {
-      PLAN_TRY(plan_malloc(&p->bwd_erec, sizeof(uint32_t) * 2 * (size_t)E));
-      // row chunks: the workspace holds one chunk's products
-      int P = o.bwd_tp_chunks > 0
-                  ? o.bwd_tp_chunks
-                  : (int)std::max<int64_t>(1, (int64_t)std::ceil((double)E * k * 4.0 /
-                                                                  kBwdTwoPassWorkspaceCap));
-      P = std::max(1, std::min(P, std::max(N, 1)));
-      p->bwd_tp_chunks = P;
-      p->tp_rows.assign(P + 1, 0);
-      p->tp_edges.assign(P + 1, 0);
-      int64_t max_chunk = 0;
-      for (int q = 1; q <= P; ++q) {
-        int32_t r = N;
-        if (q < P) {
-          // a multiple of R: the row pass's wavefronts stage rows r0 .. r0 + R - 1 with
-          // r0 % R == 0 (the edge records carry row % R)
-          const int64_t target = E * q / P;
-          r = (int32_t)(std::lower_bound(hp.begin(), hp.end(), (int32_t)target) - hp.begin());
-          r = std::max(p->tp_rows[q - 1], std::min(r / R * R, N));
-        }
-        p->tp_rows[q] = r;
-        p->tp_edges[q] = hp[r];
-        max_chunk = std::max<int64_t>(max_chunk, p->tp_edges[q] - p->tp_edges[q - 1]);
-      }
-      p->bwd_ws_bytes = max_chunk * k * 4;  // one row chunk of the E x k product workspace
-      if (!p->external_ws) {
-        PLAN_TRY(hipMalloc(&p->bwd_tbuf, (size_t)p->bwd_ws_bytes));
-        p->device_bytes += p->bwd_ws_bytes;
-      }
-      p->device_bytes += (int64_t)E * 12;  // erec + bwd_perm
-      hipLaunchKernelGGL(build_erec_kernel, dim3(grid_for(E, 256)), dim3(256), 0, s, idx,
-                         row_of, R, val, E, p->bwd_erec);
-    } else {
-      PLAN_TRY(hipMalloc(&brow, sizeof(int32_t) * E));
-      PLAN_TRY(hipMalloc(&bcol, sizeof(int32_t) * E));
-      hipLaunchKernelGGL(gather_bwd_kernel, dim3(grid_for(E, 256)), dim3(256), 0, s,
-                         p->bwd_perm, row_of, idx, E, brow, bcol, bcolpos);
+    if (!ctx.twopass) p->bwd_row_order = ctx.row_hash ? 2 : 1;
+  }
+  return MAXK_OK;
+}
+
+// offs[blk] = first sorted edge of block blk, blk in [0, nblocks], from the sorted block keys
+// (which are not needed after this).
+static hipError_t block_offsets(PlanBuild& ctx, DeviceBuf<int32_t>& d_offs) {
+  const hipError_t e = d_offs.alloc((size_t)ctx.nblocks + 1);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(key_offsets_kernel, dim3(ctx.nblocks / 256 + 1), dim3(256), 0, ctx.s,
+                     ctx.bkeys, ctx.E, ctx.nblocks, d_offs);
+  return hipGetLastError();
+}
+
+// Two-pass metadata: CSR-order edge records, row chunks, column pointers (per chunk with more
+// than one chunk). Scratch: the chunk rows' device copy, dead at return.
+static int build_two_pass(PlanBuild& ctx) {
+  maxk_plan* p = ctx.plan.get();
+  const maxk_plan_options& o = ctx.o;
+  const std::vector<int32_t>& hp = ctx.hp;
+  const int32_t N = ctx.N, NC = ctx.NC, k = ctx.k;
+  const int64_t E = ctx.E;
+  const int R = p->bwd_tp_rows;
+  hipStream_t s = ctx.s;
+  PLAN_TRY(plan_alloc(p, p->bwd_erec, 2 * (size_t)E, true));
+  // row chunks: the workspace holds one chunk's products
+  int P = o.bwd_tp_chunks > 0
+              ? o.bwd_tp_chunks
+              : (int)std::max<int64_t>(1, (int64_t)std::ceil((double)E * k * 4.0 /
+                                                              kBwdTwoPassWorkspaceCap));
+  P = std::max(1, std::min(P, std::max(N, 1)));
+  p->bwd_tp_chunks = P;
+  p->tp_rows.assign(P + 1, 0);
+  p->tp_edges.assign(P + 1, 0);
+  int64_t max_chunk = 0;
+  for (int q = 1; q <= P; ++q) {
+    int32_t r = N;
+    if (q < P) {
+      // a multiple of R: the row pass's wavefronts stage rows r0 .. r0 + R - 1 with
+      // r0 % R == 0 (the edge records carry row % R)
+      const int64_t target = E * q / P;
+      r = (int32_t)(std::lower_bound(hp.begin(), hp.end(), (int32_t)target) - hp.begin());
+      r = std::max(p->tp_rows[q - 1], std::min(r / R * R, N));
     }
-    PLAN_TRY(hipMalloc(&d_offs, sizeof(int32_t) * (nblocks + 1)));
-    hipLaunchKernelGGL(key_offsets_kernel, dim3(nblocks / 256 + 1), dim3(256), 0, s, keys_out,
-                       E, nblocks, d_offs);
+    p->tp_rows[q] = r;
+    p->tp_edges[q] = hp[r];
+    max_chunk = std::max<int64_t>(max_chunk, p->tp_edges[q] - p->tp_edges[q - 1]);
+  }
+  p->bwd_ws_bytes = max_chunk * k * 4;  // one row chunk of the E x k product workspace
+  if (!p->external_ws) PLAN_TRY(plan_alloc(p, p->bwd_tbuf, (size_t)(max_chunk * k)));
+  hipLaunchKernelGGL(build_erec_kernel, dim3(grid_for(E, 256)), dim3(256), 0, s, ctx.idx,
+                     ctx.row_of, R, ctx.val, E, p->bwd_erec);
+  DeviceBuf<int32_t> d_offs;
+  PLAN_TRY(block_offsets(ctx, d_offs));
+  // column pointers of the column-sorted edge list stay on the device
+  plan_adopt(p, p->bwd_colptr, std::move(d_offs));
+  if (P > 1) {
+    // per-chunk column pointers (rows ascend within a column of the stable sort)
+    DeviceBuf<int32_t> d_rows;
+    PLAN_TRY(d_rows.alloc((size_t)P + 1));
+    PLAN_TRY(upload(d_rows, p->tp_rows, s));
+    PLAN_TRY(plan_alloc(p, p->bwd_colptr2, (size_t)(P + 1) * NC));
+    const int64_t n = (int64_t)(P + 1) * NC;
+    hipLaunchKernelGGL(tp_colptr_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
+                       p->bwd_colptr, p->bwd_perm, ctx.row_of, NC, d_rows, P, p->bwd_colptr2);
     PLAN_TRY(hipGetLastError());
-    if (twopass) {
-      // column pointers of the column-sorted edge list stay on the device
-      p->bwd_colptr = d_offs;
-      d_offs = nullptr;
-      p->device_bytes += sizeof(int32_t) * (nblocks + 1);
-      if (p->bwd_tp_chunks > 1) {
-        // per-chunk column pointers (rows ascend within a column of the stable sort)
-        const int P = p->bwd_tp_chunks;
-        int32_t* d_rows = nullptr;
-        const hipError_t ce = [&]() -> hipError_t {
-          hipError_t e = hipMalloc(&d_rows, sizeof(int32_t) * (P + 1));
-          if (e == hipSuccess) e = hipMemcpyAsync(d_rows, p->tp_rows.data(), sizeof(int32_t) * (P + 1),
-                                                  hipMemcpyHostToDevice, s);
-          if (e == hipSuccess) e = hipMalloc(&p->bwd_colptr2, sizeof(int32_t) * (size_t)(P + 1) * NC);
-          if (e != hipSuccess) return e;
-          const int64_t n = (int64_t)(P + 1) * NC;
-          hipLaunchKernelGGL(tp_colptr_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
-                             p->bwd_colptr, p->bwd_perm, row_of, NC, d_rows, P, p->bwd_colptr2);
-          e = hipGetLastError();
-          return e == hipSuccess ? hipStreamSynchronize(s) : e;
-        }();
-        dfree(d_rows);
-        PLAN_TRY(ce);
-        p->device_bytes += sizeof(int32_t) * (int64_t)(P + 1) * NC;
-      }
-      PLAN_TRY(hipStreamSynchronize(s));
-    } else {
-      std::vector<int32_t> offs32(nblocks + 1);
-      PLAN_TRY(hipMemcpyAsync(offs32.data(), d_offs, sizeof(int32_t) * (nblocks + 1),
-                              hipMemcpyDeviceToHost, s));
-      PLAN_TRY(hipStreamSynchronize(s));
-      for (int b = 0; b <= nblocks; ++b) offs[b] = offs32[b];
-    }
+    PLAN_TRY(hipStreamSynchronize(s));  // d_rows is freed at return
   }
-  std::vector<BwdTask> btasks;
-  int nshared = 0;
-  if (!twopass && E > 0 && nblocks > 0) {
-    // Task count: about kBwdTasksPerCu work-groups per CU, each of its block's chunks with
-    // >= kBwdMinTaskEdges edges (every chunk clears and stores its whole block, C * k
-    // floats), but not fewer tasks than CUs while those keep >= 4k edges (a row shard of an
-    // 8-GPU partition: 256 tasks of ~56k edges ran 0.24 ms, 512 of ~28k 0.27, 128 0.40)
-    const int64_t target_tasks = (int64_t)(o.bwd_tasks_per_cu ? o.bwd_tasks_per_cu : kBwdTasksPerCu) * cus;
-    const int64_t bS = (int64_t)nblocks * S;
-    const int64_t chunks = std::max<int64_t>(1, (target_tasks + bS - 1) / bS);
-    const int64_t min_task_edges = o.bwd_min_task_edges > 0 ? o.bwd_min_task_edges : kBwdMinTaskEdges;
-    int64_t nch64 = std::min<int64_t>(chunks, E / ((int64_t)nblocks * min_task_edges));
-    const int64_t fl = ((int64_t)cus + bS - 1) / bS;
-    if (o.bwd_min_task_edges == 0 && nch64 < fl && E / ((int64_t)nblocks * fl) >= 4096)
-      nch64 = std::min<int64_t>(chunks, fl);
-    nch64 = std::max<int64_t>(1, nch64);
-    // One work-group per CU: a task count just past a multiple of the CUs leaves the last
-    // round mostly idle (ogbn-proteins k = 32: 192 blocks x 3 chunks = 2.25 rounds, 2.37 ms;
-    // x 4 = 3 rounds, 1.82 ms). With the default knobs take, among the chunk counts from one
-    // round of tasks (fl) up to nch + 2 (keeping >= 0.6 x the minimum task above nch), the
-    // FEWEST whose tasks fill their rounds within 0.05 of the best: every task zeroes and
-    // stores its block and stages its selectors, so with the counter-fed 16-wave work-groups
-    // one full round beats two (Reddit k = 8 / 16 / 32: 512 -> 256 tasks -2.8 / -2.0 / -1.8 %,
-    // ogbn-proteins k = 16 -1.4 %; profiles/r05/bwd_task_rounds.jsonl)
-    if (o.bwd_tasks_per_cu == 0 && o.bwd_min_task_edges == 0) {
-      auto fill = [&](int64_t c) {
-        const int64_t t = bS * c;
-        return (double)t / ((double)((t + cus - 1) / cus) * cus);
-      };
-      // the fill counts tasks, not edges: go below nch only while the blocks hold similar edge
-      // counts (largest <= 2x the mean), so a skewed block cannot become a one-round tail
-      // 
-      int64_t max_nnz = 0;
-      for (int b = 0; b < nblocks; ++b) max_nnz = std::max<int64_t>(max_nnz, offs[b + 1] - offs[b]);
-      const bool even_blocks = max_nnz * (int64_t)nblocks <= 2 * E;
-      const int64_t lo = even_blocks ? std::max<int64_t>(1, std::min(nch64, fl)) : nch64;
-      int64_t hi = nch64;
-      for (int64_t c = nch64 + 1; c <= nch64 + 2; ++c) {
-        if ((double)E / ((double)nblocks * c) < 0.6 * kBwdMinTaskEdges) break;
-        hi = c;
-      }
-      double bestf = 0.0;
-      for (int64_t c = lo; c <= hi; ++c) bestf = std::max(bestf, fill(c));
-      int64_t best = hi;
-      for (int64_t c = lo; c <= hi; ++c)
-        if (fill(c) >= bestf - 0.05) { best = c; break; }
-      nch64 = best;
-    }
-    const int nch = (int)nch64;
-    // Chunk j of block b holds edges [j, j+1) * nnz_b / nch of the block's row-sorted stream.
-    // On a graph without column locality these are about the same row bounds in every block
-    // (the work-groups that run together sweep the same rows of G); with locality (a
-    // community linking mostly into its own blocks) every task keeps an equal share instead
-    // of a few tasks carrying most of a chunk (41-community Reddit-size graph, k = 16: 3.38
-    // -> 2.18 ms; the scattered row order then takes it to 1.60).
-    std::vector<std::vector<int32_t>> cbd((size_t)nblocks);
-    for (int b = 0; b < nblocks; ++b) {
-      const int64_t o0 = offs[b], nnz = offs[b + 1] - offs[b];
-      cbd[b].resize(nch + 1);
-      for (int j = 0; j <= nch; ++j) cbd[b][j] = (int32_t)(o0 + nnz * j / nch);
-    }
-    // Pieces: a (block, chunk) task holding more than twice the average task's edges is cut
-    // into pieces of equal edge counts (work-groups of their own).
-    const int64_t avg_task = std::max<int64_t>(1, E / ((int64_t)nblocks * nch));
-    const int64_t piece_cap = o.bwd_piece_edges > 0 ? (int64_t)o.bwd_piece_edges
-                                                    : std::max<int64_t>(2 * avg_task, 16384);
-    const bool slab_flush = o.bwd_flush != 1;
-    auto npieces = [&](int64_t e) {
-      return (int32_t)std::max<int64_t>(1, (e + piece_cap - 1) / piece_cap);
+  PLAN_TRY(hipStreamSynchronize(s));
+  return MAXK_OK;
+}
+
+// Column blocks: block position and destination row of each reordered edge (brow / bcol, kept
+// for the first-row gather and the records), and the blocks' edge offsets on the host. Runs
+// after the idx validation: gather_bwd_kernel indexes colpos with unclamped column ids.
+static int gather_block_edges(PlanBuild& ctx) {
+  maxk_plan* p = ctx.plan.get();
+  const int64_t E = ctx.E;
+  hipStream_t s = ctx.s;
+  PLAN_TRY(ctx.brow.alloc((size_t)E));
+  PLAN_TRY(ctx.bcol.alloc((size_t)E));
+  hipLaunchKernelGGL(gather_bwd_kernel, dim3(grid_for(E, 256)), dim3(256), 0, s, p->bwd_perm,
+                     ctx.row_of, ctx.idx, E, ctx.brow, ctx.bcol, ctx.bcolpos);
+  DeviceBuf<int32_t> d_offs;
+  PLAN_TRY(block_offsets(ctx, d_offs));
+  std::vector<int32_t> offs32(ctx.nblocks + 1);
+  PLAN_TRY(hipMemcpyAsync(offs32.data(), d_offs, sizeof(int32_t) * (ctx.nblocks + 1),
+                          hipMemcpyDeviceToHost, s));
+  PLAN_TRY(hipStreamSynchronize(s));
+  for (int blk = 0; blk <= ctx.nblocks; ++blk) ctx.offs[blk] = offs32[blk];
+  return MAXK_OK;
+}
+
+// Chunks per column block (host only).
+static int bwd_chunk_count(const PlanBuild& ctx) {
+  const maxk_plan_options& o = ctx.o;
+  const std::vector<int64_t>& offs = ctx.offs;
+  const int64_t E = ctx.E;
+  const int nblocks = ctx.nblocks, S = ctx.S, cus = ctx.plan->cus;
+  // Task count: about kBwdTasksPerCu work-groups per CU, each of its block's chunks with
+  // >= kBwdMinTaskEdges edges (every chunk clears and stores its whole block, C * k
+  // floats), but not fewer tasks than CUs while those keep >= 4k edges (a row shard of an
+  // 8-GPU partition: 256 tasks of ~56k edges ran 0.24 ms, 512 of ~28k 0.27, 128 0.40)
+  const int64_t target_tasks = (int64_t)(o.bwd_tasks_per_cu ? o.bwd_tasks_per_cu : kBwdTasksPerCu) * cus;
+  const int64_t bS = (int64_t)nblocks * S;
+  const int64_t chunks = std::max<int64_t>(1, (target_tasks + bS - 1) / bS);
+  const int64_t min_task_edges = o.bwd_min_task_edges > 0 ? o.bwd_min_task_edges : kBwdMinTaskEdges;
+  int64_t nch64 = std::min<int64_t>(chunks, E / ((int64_t)nblocks * min_task_edges));
+  const int64_t fl = ((int64_t)cus + bS - 1) / bS;
+  if (o.bwd_min_task_edges == 0 && nch64 < fl && E / ((int64_t)nblocks * fl) >= 4096)
+    nch64 = std::min<int64_t>(chunks, fl);
+  nch64 = std::max<int64_t>(1, nch64);
+  // One work-group per CU: a task count just past a multiple of the CUs leaves the last
+  // round mostly idle (ogbn-proteins k = 32: 192 blocks x 3 chunks = 2.25 rounds, 2.37 ms;
+  // x 4 = 3 rounds, 1.82 ms). With the default knobs take, among the chunk counts from one
+  // round of tasks (fl) up to nch + 2 (keeping >= 0.6 x the minimum task above nch), the
+  // FEWEST whose tasks fill their rounds within 0.05 of the best: every task zeroes and
+  // stores its block and stages its selectors, so with the counter-fed 16-wave work-groups
+  // one full round beats two (Reddit k = 8 / 16 / 32: 512 -> 256 tasks -2.8 / -2.0 / -1.8 %,
+  // ogbn-proteins k = 16 -1.4 %; profiles/r05/bwd_task_rounds.jsonl)
+  if (o.bwd_tasks_per_cu == 0 && o.bwd_min_task_edges == 0) {
+    auto fill = [&](int64_t c) {
+      const int64_t t = bS * c;
+      return (double)t / ((double)((t + cus - 1) / cus) * cus);
     };
-    std::vector<int32_t> pieces_of((size_t)nblocks, 0);
-    for (int b = 0; b < nblocks; ++b)
-      for (int j = 0; j < nch; ++j) pieces_of[b] += npieces((int64_t)cbd[b][j + 1] - cbd[b][j]);
-    // compact slab regions: block b's pieces 1 .. P_b - 1 own C x k floats each
-    std::vector<int64_t> slab_base((size_t)nblocks, -1);
-    std::vector<int4> comb;
-    int64_t slab_floats = 0;
-    for (int b = 0; b < nblocks; ++b) {
-      if (pieces_of[b] > 1) ++nshared;
-      if (slab_flush && pieces_of[b] > 1) {
-        slab_base[b] = slab_floats;
-        const int ncols_b = std::min(C, NC - b * C);
-        comb.push_back(make_int4((int)slab_floats, pieces_of[b] - 1, b * C, ncols_b));
-        slab_floats += (int64_t)(pieces_of[b] - 1) * C * k;
-      }
+    // the fill counts tasks, not edges: go below nch only while the blocks hold similar edge
+    // counts (largest <= 2x the mean), so a skewed block cannot become a one-round tail
+    // 
+    int64_t max_nnz = 0;
+    for (int b = 0; b < nblocks; ++b) max_nnz = std::max<int64_t>(max_nnz, offs[b + 1] - offs[b]);
+    const bool even_blocks = max_nnz * (int64_t)nblocks <= 2 * E;
+    const int64_t lo = even_blocks ? std::max<int64_t>(1, std::min(nch64, fl)) : nch64;
+    int64_t hi = nch64;
+    for (int64_t c = nch64 + 1; c <= nch64 + 2; ++c) {
+      if ((double)E / ((double)nblocks * c) < 0.6 * kBwdMinTaskEdges) break;
+      hi = c;
     }
-    if (slab_floats >= (int64_t)INT32_MAX) {  // task offsets are int32: flush atomically
-      comb.clear();
-      slab_floats = 0;
-      std::fill(slab_base.begin(), slab_base.end(), -1);
-    }
-    // Row-major emission: chunks ordered by the first destination row they sweep (then by
-    // block), so the work-groups that run together sweep about the same rows of G and share
-    // its lines in L2; work-group i runs on XCD i % 8 (dealt round-robin; speed only), so
-    // consecutive tasks spread over the XCDs and every XCD gets the same share.
-    std::vector<int32_t> first_row((size_t)nblocks * nch);
-    {
-      std::vector<int32_t> starts;
-      for (int b = 0; b < nblocks; ++b)
-        for (int j = 0; j < nch; ++j)
-          starts.push_back(std::min<int32_t>(cbd[b][j], (int32_t)std::max<int64_t>(E - 1, 0)));
-      int32_t *d_st = nullptr, *d_fr = nullptr;
-      const hipError_t fe = [&]() -> hipError_t {
-        hipError_t e = hipMalloc(&d_st, sizeof(int32_t) * starts.size());
-        if (e == hipSuccess) e = hipMalloc(&d_fr, sizeof(int32_t) * starts.size());
-        if (e == hipSuccess) e = hipMemcpyAsync(d_st, starts.data(), sizeof(int32_t) * starts.size(),
-                                                hipMemcpyHostToDevice, s);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(gather_i32_kernel, dim3((unsigned)((starts.size() + 255) / 256)),
-                           dim3(256), 0, s, brow, d_st, (int)starts.size(), d_fr);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(first_row.data(), d_fr, sizeof(int32_t) * starts.size(),
-                                                hipMemcpyDeviceToHost, s);
-        return e == hipSuccess ? hipStreamSynchronize(s) : e;
-      }();
-      dfree(d_st);
-      dfree(d_fr);
-      PLAN_TRY(fe);
-    }
-    struct ChunkRef { int64_t row; int b, j; };
-    std::vector<ChunkRef> order_c;
-    for (int b = 0; b < nblocks; ++b)
-      for (int j = 0; j < nch; ++j) order_c.push_back(ChunkRef{row_pos(first_row[(size_t)b * nch + j]), b, j});
-    std::stable_sort(order_c.begin(), order_c.end(),
-                     [](const ChunkRef& a, const ChunkRef& b) { return a.row < b.row; });
-    // a block's chunks must come in chunk order (piece numbering, slab regions)
-    std::vector<int32_t> next_chunk((size_t)nblocks, 0);
-    for (ChunkRef& cr : order_c) cr.j = next_chunk[cr.b]++;
-    std::vector<int32_t> next_piece((size_t)nblocks, 0);
-    for (const ChunkRef& cr : order_c) {
-      const int b = cr.b;
-      const int32_t e0 = cbd[b][cr.j], e1 = cbd[b][cr.j + 1];
-      const int np = npieces((int64_t)e1 - e0);
-      for (int q = 0; q < np; ++q) {
-        const int piece = next_piece[b]++;
-        for (int g = 0; g < S; ++g) {  // the groups of a block share its edge stream
-          BwdTask t{};
-          t.col0 = b * C;
-          t.ncols = std::min(C, NC - t.col0);
-          t.e0 = (int32_t)(e0 + ((int64_t)e1 - e0) * q / np);
-          t.e1 = (int32_t)(e0 + ((int64_t)e1 - e0) * (q + 1) / np);
-          t.shared = pieces_of[b] > 1;
-          t.group = g;
-          t.chunk = piece;
-          t.slab = (slab_base[b] >= 0 && piece > 0)
-                       ? (int32_t)(slab_base[b] + (int64_t)(piece - 1) * C * k) : -1;
-          btasks.push_back(t);
-        }
-      }
-    }
-    if (!comb.empty()) {
-      p->bwd_slab_floats = slab_floats;
-      p->n_bwd_combine = (int32_t)comb.size();
-      PLAN_TRY(hipMalloc(&p->bwd_combine, sizeof(int4) * comb.size()));
-      PLAN_TRY(hipMemcpyAsync(p->bwd_combine, comb.data(), sizeof(int4) * comb.size(),
-                              hipMemcpyHostToDevice, s));
-      PLAN_TRY(hipStreamSynchronize(s));
-      p->device_bytes += sizeof(int4) * comb.size();
+    double bestf = 0.0;
+    for (int64_t c = lo; c <= hi; ++c) bestf = std::max(bestf, fill(c));
+    int64_t best = hi;
+    for (int64_t c = lo; c <= hi; ++c)
+      if (fill(c) >= bestf - 0.05) { best = c; break; }
+    nch64 = best;
+  }
+  return (int)nch64;
+}
+
+// Column-block task emission: chunk bounds, pieces, slabs and the combine list, the tasks in
+// first-row order. Host only apart from the first_row gather, whose two device arrays and host
+// table die with its block, after its synchronise; the combine list's upload is synchronised
+// here too (its source is local).
+static int emit_block_tasks(PlanBuild& ctx) {
+  maxk_plan* p = ctx.plan.get();
+  const maxk_plan_options& o = ctx.o;
+  const std::vector<int64_t>& offs = ctx.offs;
+  std::vector<BwdTask>& btasks = ctx.btasks;
+  const int32_t N = ctx.N, NC = ctx.NC, k = ctx.k;
+  const int64_t E = ctx.E;
+  const int nblocks = ctx.nblocks, C = ctx.C, S = ctx.S;
+  hipStream_t s = ctx.s;
+  auto row_pos = [&](int32_t r) -> int64_t {
+    return ctx.row_hash ? (ctx.ra * (int64_t)r + ctx.rb) % N : r;
+  };
+  const int nch = bwd_chunk_count(ctx);
+  // Chunk j of block b holds edges [j, j+1) * nnz_b / nch of the block's row-sorted stream.
+  // On a graph without column locality these are about the same row bounds in every block
+  // (the work-groups that run together sweep the same rows of G); with locality (a
+  // community linking mostly into its own blocks) every task keeps an equal share instead
+  // of a few tasks carrying most of a chunk (41-community Reddit-size graph, k = 16: 3.38
+  // -> 2.18 ms; the scattered row order then takes it to 1.60).
+  std::vector<std::vector<int32_t>> cbd((size_t)nblocks);
+  for (int b = 0; b < nblocks; ++b) {
+    const int64_t o0 = offs[b], nnz = offs[b + 1] - offs[b];
+    cbd[b].resize(nch + 1);
+    for (int j = 0; j <= nch; ++j) cbd[b][j] = (int32_t)(o0 + nnz * j / nch);
+  }
+  // Pieces: a (block, chunk) task holding more than twice the average task's edges is cut
+  // into pieces of equal edge counts (work-groups of their own).
+  const int64_t avg_task = std::max<int64_t>(1, E / ((int64_t)nblocks * nch));
+  const int64_t piece_cap = o.bwd_piece_edges > 0 ? (int64_t)o.bwd_piece_edges
+                                                  : std::max<int64_t>(2 * avg_task, 16384);
+  const bool slab_flush = o.bwd_flush != 1;
+  auto npieces = [&](int64_t e) {
+    return (int32_t)std::max<int64_t>(1, (e + piece_cap - 1) / piece_cap);
+  };
+  std::vector<int32_t> pieces_of((size_t)nblocks, 0);
+  for (int b = 0; b < nblocks; ++b)
+    for (int j = 0; j < nch; ++j) pieces_of[b] += npieces((int64_t)cbd[b][j + 1] - cbd[b][j]);
+  // compact slab regions: block b's pieces 1 .. P_b - 1 own C x k floats each
+  std::vector<int64_t> slab_base((size_t)nblocks, -1);
+  std::vector<int4> comb;
+  int64_t slab_floats = 0;
+  for (int b = 0; b < nblocks; ++b) {
+    if (pieces_of[b] > 1) ++ctx.nshared;
+    if (slab_flush && pieces_of[b] > 1) {
+      slab_base[b] = slab_floats;
+      const int ncols_b = std::min(C, NC - b * C);
+      comb.push_back(make_int4((int)slab_floats, pieces_of[b] - 1, b * C, ncols_b));
+      slab_floats += (int64_t)(pieces_of[b] - 1) * C * k;
     }
   }
+  if (slab_floats >= (int64_t)INT32_MAX) {  // task offsets are int32: flush atomically
+    comb.clear();
+    slab_floats = 0;
+    std::fill(slab_base.begin(), slab_base.end(), -1);
+  }
+  // Row-major emission: chunks ordered by the first destination row they sweep (then by
+  // block), so the work-groups that run together sweep about the same rows of G and share
+  // its lines in L2; work-group i runs on XCD i % 8 (dealt round-robin; speed only), so
+  // consecutive tasks spread over the XCDs and every XCD gets the same share.
+  std::vector<int32_t> first_row((size_t)nblocks * nch);
+  {
+    std::vector<int32_t> starts;
+    for (int b = 0; b < nblocks; ++b)
+      for (int j = 0; j < nch; ++j)
+        starts.push_back(std::min<int32_t>(cbd[b][j], (int32_t)std::max<int64_t>(E - 1, 0)));
+    DeviceBuf<int32_t> d_st, d_fr;
+    PLAN_TRY(d_st.alloc(starts.size()));
+    PLAN_TRY(d_fr.alloc(starts.size()));
+    PLAN_TRY(upload(d_st, starts, s));
+    hipLaunchKernelGGL(gather_i32_kernel, dim3((unsigned)((starts.size() + 255) / 256)), dim3(256),
+                       0, s, ctx.brow, d_st, (int)starts.size(), d_fr);
+    PLAN_TRY(hipGetLastError());
+    PLAN_TRY(hipMemcpyAsync(first_row.data(), d_fr, sizeof(int32_t) * starts.size(),
+                            hipMemcpyDeviceToHost, s));
+    PLAN_TRY(hipStreamSynchronize(s));
+  }
+  struct ChunkRef { int64_t row; int b, j; };
+  std::vector<ChunkRef> order_c;
+  for (int b = 0; b < nblocks; ++b)
+    for (int j = 0; j < nch; ++j) order_c.push_back(ChunkRef{row_pos(first_row[(size_t)b * nch + j]), b, j});
+  std::stable_sort(order_c.begin(), order_c.end(),
+                   [](const ChunkRef& a, const ChunkRef& b) { return a.row < b.row; });
+  // a block's chunks must come in chunk order (piece numbering, slab regions)
+  std::vector<int32_t> next_chunk((size_t)nblocks, 0);
+  for (ChunkRef& cr : order_c) cr.j = next_chunk[cr.b]++;
+  std::vector<int32_t> next_piece((size_t)nblocks, 0);
+  for (const ChunkRef& cr : order_c) {
+    const int b = cr.b;
+    const int32_t e0 = cbd[b][cr.j], e1 = cbd[b][cr.j + 1];
+    const int np = npieces((int64_t)e1 - e0);
+    for (int q = 0; q < np; ++q) {
+      const int piece = next_piece[b]++;
+      for (int g = 0; g < S; ++g) {  // the groups of a block share its edge stream
+        BwdTask t{};
+        t.col0 = b * C;
+        t.ncols = std::min(C, NC - t.col0);
+        t.e0 = (int32_t)(e0 + ((int64_t)e1 - e0) * q / np);
+        t.e1 = (int32_t)(e0 + ((int64_t)e1 - e0) * (q + 1) / np);
+        t.shared = pieces_of[b] > 1;
+        t.group = g;
+        t.chunk = piece;
+        t.slab = (slab_base[b] >= 0 && piece > 0)
+                     ? (int32_t)(slab_base[b] + (int64_t)(piece - 1) * C * k) : -1;
+        btasks.push_back(t);
+      }
+    }
+  }
+  if (!comb.empty()) {
+    p->bwd_slab_floats = slab_floats;
+    p->n_bwd_combine = (int32_t)comb.size();
+    PLAN_TRY(plan_alloc(p, p->bwd_combine, comb.size()));
+    PLAN_TRY(upload(p->bwd_combine, comb, s));
+    PLAN_TRY(hipStreamSynchronize(s));
+  }
+  return MAXK_OK;
+}
+
+// XCD dealing of the emitted tasks (host only).
+static void deal_to_xcds(PlanBuild& ctx) {
+  const maxk_plan_options& o = ctx.o;
+  std::vector<BwdTask>& btasks = ctx.btasks;
+  const int cus = ctx.plan->cus;
   // default on (Reddit k = 16: 1.665 -> 1.626 ms, an 8-GPU row shard 0.241 -> 0.226). Round 4
   // measured them +0.7-1.5 % with two slot groups (profiles/r04/bwd_order_ab.jsonl); with the
   // round-5 kernel (counter-fed 16 waves, one round) they gain there too: k = 16 / 24 / 32 / 64
@@ -1401,8 +1499,16 @@ static int plan_create_impl(const int32_t* ptr, const int32_t* idx, const float*
     }
     btasks.swap(dealt);
   }
-  p->n_bwd_tasks = (int32_t)btasks.size();
-  p->n_bwd_shared = nshared;
+}
+
+// The wave / unroll / hand-out shape that actually launches (host only).
+static void resolve_launch_shape(PlanBuild& ctx) {
+  maxk_plan* p = ctx.plan.get();
+  const maxk_plan_options& o = ctx.o;
+  const int32_t k = ctx.k;
+  const int cus = p->cus;
+  p->n_bwd_tasks = (int32_t)ctx.btasks.size();
+  p->n_bwd_shared = ctx.nshared;
   // window hand-out (profiles/r05/handout_ab.jsonl): the backward always takes
   // its windows from an LDS counter (k = 8..64 -2..-6 %, W = 8 shards -2 %); the forward with
   // 8 waves and at k <= 16 (-0.3 %, W = 8 shards -1..-5 %); 4 waves above k = 16 keep the
@@ -1433,40 +1539,79 @@ static int plan_create_impl(const int32_t* ptr, const int32_t* idx, const float*
     p->bwd_waves = 8;
     p->bwd_unroll = 8;
   }
-  if (!btasks.empty()) {
-    PLAN_TRY(hipMalloc(&p->bwd_tasks, sizeof(BwdTask) * btasks.size()));
-    PLAN_TRY(hipMemcpyAsync(p->bwd_tasks, btasks.data(), sizeof(BwdTask) * btasks.size(),
-                            hipMemcpyHostToDevice, s));
-    p->device_bytes += sizeof(BwdTask) * btasks.size();
+}
+
+// Uploads and the record build; the column order moves into the plan when the column blocks
+// use it. btasks lives in the context, so its copy needs no synchronise of its own.
+static int upload_backward(PlanBuild& ctx) {
+  maxk_plan* p = ctx.plan.get();
+  const int64_t E = ctx.E;
+  hipStream_t s = ctx.s;
+  if (!ctx.btasks.empty()) {
+    PLAN_TRY(plan_alloc(p, p->bwd_tasks, ctx.btasks.size()));
+    PLAN_TRY(upload(p->bwd_tasks, ctx.btasks, s));
   }
-  if (!twopass && E > 0) {
+  if (!ctx.twopass && E > 0) {
     // the column blocks' records (padded: a wave may read past the last task's end)
-    PLAN_TRY(plan_malloc(&p->bwd_rec, sizeof(uint32_t) * 3 * (size_t)(E + kBwdRecPad)));
+    PLAN_TRY(plan_alloc(p, p->bwd_rec, 3 * (size_t)(E + kBwdRecPad), true));
     PLAN_TRY(hipMemsetAsync(p->bwd_rec + 3 * E, 0, sizeof(uint32_t) * 3 * kBwdRecPad, s));
-    hipLaunchKernelGGL(build_bwd_rec_kernel, dim3(grid_for(E, 256)), dim3(256), 0, s, p->bwd_perm,
-                       brow, bcol, val, E, C, D, p->bwd_big, p->bwd_rec);
+    hipLaunchKernelGGL(build_bwd_rec_kernel, dim3(grid_for(E, 256)), dim3(256), 0, s,
+                       p->bwd_perm, ctx.brow, ctx.bcol, ctx.val, E, ctx.C, ctx.D,
+                       p->bwd_big, p->bwd_rec);
     PLAN_TRY(hipGetLastError());
     // per-call workspace: the slab regions of split blocks (the kernel stages the selectors
     // from sp_index itself; no selector words since round 5)
     p->bwd_slab_off = 0;
     p->bwd_ws_bytes = p->bwd_slab_floats * 4;
     if (!p->external_ws && p->bwd_ws_bytes > 0)
-      PLAN_TRY(hipMalloc(&p->bwd_sel, (size_t)p->bwd_ws_bytes));
-    p->device_bytes += (int64_t)E * 16 + 12ll * kBwdRecPad + (!p->external_ws ? p->bwd_ws_bytes : 0);
+      PLAN_TRY(plan_alloc(p, p->bwd_sel, (size_t)p->bwd_slab_floats));
   }
   PLAN_TRY(hipStreamSynchronize(s));
   // the column order stays with the plan when the column blocks use it
   p->col_order = 1;
-  if (order && bcolpos) {
-    p->col_order = order_mode;
-    p->bwd_corder = order;
-    p->device_bytes += sizeof(int32_t) * (int64_t)NC;
-    order = nullptr;
+  if (ctx.order && ctx.bcolpos) {
+    p->col_order = ctx.order_mode;
+    plan_adopt(p, p->bwd_corder, std::move(ctx.order));
   }
-  dfree(order); dfree(colpos); dfree(row_of); dfree(keys_in); dfree(keys_out); dfree(ids_in);
-  dfree(brow); dfree(bcol); dfree(temp); dfree(d_offs); dfree(d_bad);
+  return MAXK_OK;
+}
 #undef PLAN_TRY
-  *out_plan = p;
+
+static int plan_create_impl(const int32_t* ptr, const int32_t* idx, const float* val, int32_t N,
+                            int32_t NC, int64_t E, int32_t D, int32_t k,
+                            const maxk_plan_options& o, const int32_t* user_order, void* stream,
+                            maxk_plan** out_plan) {
+  *out_plan = nullptr;
+  PlanBuild ctx{ptr, idx, val, N, NC, E, D, k, o, user_order, (hipStream_t)stream};
+  if (const int rc = check_args(ctx)) return rc;
+  ctx.plan.reset(new maxk_plan());
+  maxk_plan* p = ctx.plan.get();
+  p->external_ws = o.external_workspace;
+  p->num_nodes = N;
+  p->num_cols = NC;
+  p->num_edges = E;
+  p->dim_origin = D;
+  p->dim_k = k;
+  p->src_ptr = ptr;
+  p->src_idx = idx;
+  p->cus = device_cus();
+  choose_fwd_shape(ctx);
+  choose_bwd_shape(ctx);
+  int rc = read_ptr(ctx);
+  if (rc == MAXK_OK) rc = build_column_order(ctx);
+  if (rc == MAXK_OK) rc = build_forward(ctx);
+  if (rc == MAXK_OK) rc = layout_fwd_workspace(ctx);
+  if (rc == MAXK_OK) {
+    choose_bwd_algo(ctx);
+    rc = sort_bwd_blocks(ctx);
+  }
+  if (rc == MAXK_OK && E > 0) rc = ctx.twopass ? build_two_pass(ctx) : gather_block_edges(ctx);
+  if (rc == MAXK_OK && !ctx.twopass && E > 0 && ctx.nblocks > 0) rc = emit_block_tasks(ctx);
+  if (rc != MAXK_OK) return rc;  // the context frees the plan and every scratch buffer
+  deal_to_xcds(ctx);
+  resolve_launch_shape(ctx);
+  if (const int rc2 = upload_backward(ctx)) return rc2;
+  *out_plan = ctx.plan.release();
   return MAXK_OK;
 }
 
@@ -1563,6 +1708,6 @@ extern "C" int maxk_plan_workspace_bytes(const maxk_plan* p, int64_t* fwd_bytes,
 }
 
 extern "C" int maxk_plan_destroy(maxk_plan* p) {
-  free_plan(p);
+  delete p;  // the plan's DeviceBuf members free its arrays
   return MAXK_OK;
 }

@@ -1,7 +1,9 @@
 """GPU: what a plan holds, for how long, and which plan a call gets.
 
-plan.hip takes its 18 plan arrays and its build-time temporaries with raw ``hipMalloc``, frees
-them from hand-written lists and adds ``device_bytes`` up by hand; ``device_bytes`` is the only
+The 18 plan arrays are owning device buffers (``DeviceBuf`` members of ``maxk_plan``, freed by
+its destructor), the build's temporaries are ``DeviceBuf`` locals of the build's stages, and
+``device_bytes`` is summed by the one function that allocates a plan array (``plan_alloc``, or
+``plan_adopt`` for a scratch buffer promoted into the plan); ``device_bytes`` is the only
 input of the plan cache's byte budget, and autograd contexts keep plans alive past eviction.
 None of that changes an output, so these tests read the device's free memory instead.
 
@@ -66,7 +68,7 @@ affordable on, below what the cycles resolve; their frees are checked by the acc
 of ``split_everything``, where they are 24 MiB and more and destroy has to give back what the
 plan held.
 
-The out-of-range ``idx`` refusal is included: plan_create_impl reads the key kernel's ``bad``
+The out-of-range ``idx`` refusal is included: sort_bwd_blocks reads the key kernel's ``bad``
 flag right after the block sort, and every kernel before that point uses a column id as a value
 (sort keys, edge words) or clamped (``bwd_key_kernel``), never as an index.
 """
@@ -381,7 +383,8 @@ def raw_info(h):
 
 def nonnull_arrays(info, opts):
     """The plan arrays that are non-null, from what the plan reports and was asked for
-    (plan.hip, plan_create_impl)."""
+    (plan.hip: the stages plan_create_impl runs, each array taken through plan_alloc or
+    plan_adopt)."""
     owned = not opts.get("external_workspace", 0)
     s = set()
     if info["fwd_tasks"] > 0:
