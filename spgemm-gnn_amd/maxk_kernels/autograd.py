@@ -17,15 +17,66 @@ module that does not exist) and its ``MaxKFunction`` (utils/maxk_layers.py:16-45
   ``ops.spgemm_edge_grad`` for the values' gradient.
 * :class:`EdgeSoftmaxFunction` (:func:`edge_softmax`) normalises per-edge logits over each
   destination row's in-edges: the attention weights that ``edge_weight=`` then takes.
+
+Every backward is first order only (:func:`first_order_only`): under ``create_graph=True`` the
+gradients are the usual ones and differentiating them raises. The unweighted aggregations read
+``graph.val`` again in the backward, so they remember its version and refuse a backward after an
+in-place edit of it (``_check_values_version``).
 """
 from __future__ import annotations
 
+import functools
 from dataclasses import dataclass, field
 from typing import Optional
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import ops
+
+
+def first_order_only(backward):
+    """``once_differentiable`` for a backward whose body is kernel launches into fresh buffers,
+    which autograd cannot see through. Under ``create_graph=True`` the returned gradients carry
+    a node that raises when anything built from them is differentiated. ``once_differentiable``
+    alone attaches that node only when an incoming gradient requires grad; with a constant one
+    (``y.sum()``) it would hand back plain constants, and a gradient-penalty term built from them
+    would drop out of the second backward without an error. Here the node is attached whenever
+    the backward runs in grad mode, i.e. whenever a graph of it was asked for."""
+    once = once_differentiable(backward)
+
+    @functools.wraps(backward)
+    def wrapper(ctx, *grads):
+        if torch.is_grad_enabled() and not any(
+                isinstance(g, torch.Tensor) and g.requires_grad for g in grads):
+            grads = list(grads)
+            for i, g in enumerate(grads):
+                if isinstance(g, torch.Tensor) and g.is_floating_point():
+                    grads[i] = g.detach().requires_grad_(True)
+                    break
+        return once(ctx, *grads)
+
+    return wrapper
+
+
+def _save_values_version(ctx, val: torch.Tensor) -> None:
+    """The backward of an unweighted aggregation computes with ``graph.val`` again (through the
+    plan's snapshot, or A^T built from it): remember which version the forward ran with."""
+    ctx.val_ref, ctx.val_version = val, ops._version(val)
+
+
+def _check_values_version(ctx) -> None:
+    """Refuse a backward whose forward ran with other edge values: ``graph.val`` was edited in
+    place since (torch's wording for a saved tensor), whether or not a later forward on the same
+    graph has already refreshed the shared plan to the new values. A view of ``graph.val``
+    shares its version counter, so an edit through one is seen too."""
+    val = ctx.val_ref
+    if ops._version(val) != ctx.val_version:
+        raise RuntimeError(
+            "maxk_kernels: the graph's edge values (graph.val) needed for gradient computation "
+            f"have been modified by an inplace operation: they are at version {val._version}, "
+            f"the forward ran with version {ctx.val_version}. Run the backward before editing "
+            "graph.val, or pass the changing values as edge_weight=")
 
 
 @dataclass
@@ -158,7 +209,7 @@ class CSRGraph:
     def transposed(self) -> "CSRGraph":
         """A^T with the same edge values (row = source node), cached: the backward of the
         dense aggregation, dX = A^T dY, runs the same SpMM kernel on it."""
-        key = ("transposed", self.val.data_ptr(), self.val._version)
+        key = ("transposed", self.val.data_ptr(), ops._version(self.val))
         g = self._values.get(key)
         if g is None:
             rows = torch.repeat_interleave(torch.arange(self.num_nodes, device=self.device),
@@ -240,6 +291,7 @@ class MaxKFunction(torch.autograd.Function):
         return sp_data, sp_index
 
     @staticmethod
+    @first_order_only
     def backward(ctx, grad_data, grad_index):
         saved = ctx.saved_tensors
         sp_index = saved[0]
@@ -266,15 +318,18 @@ class SpGEMMFunction(torch.autograd.Function):
         ctx.graph = graph
         ctx.plan = plan  # the backward uses the same plan (no cache lookup, no rebuild)
         ctx.dims = (dim_origin, k)
+        _save_values_version(ctx, graph.val)
         return out
 
     @staticmethod
+    @first_order_only
     def backward(ctx, grad_out):
         (sp_index,) = ctx.saved_tensors
         graph = ctx.graph
         dim_origin, k = ctx.dims
         grad_sp = None
         if ctx.needs_input_grad[0]:
+            _check_values_version(ctx)
             grad_sp = ops.spgemm_backward(graph.ptr, graph.idx, graph.val,
                                           grad_out.contiguous(), sp_index, graph.num_nodes,
                                           graph.num_edges, k, dim_origin, plan=ctx.plan)
@@ -290,12 +345,15 @@ class DenseAggFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x: torch.Tensor, graph: CSRGraph):
         ctx.graph = graph
+        _save_values_version(ctx, graph.val)
         return ops.dense_spmm(graph.ptr, graph.idx, graph.val, x.contiguous())
 
     @staticmethod
+    @first_order_only
     def backward(ctx, grad_out):
         grad_x = None
         if ctx.needs_input_grad[0]:
+            _check_values_version(ctx)
             gt = ctx.graph.transposed()
             grad_x = ops.dense_spmm(gt.ptr, gt.idx, gt.val, grad_out.contiguous())
         return grad_x, None
@@ -340,14 +398,17 @@ class MaxKAggregateFunction(torch.autograd.Function):
         ctx.plan = plan
         ctx.dropout = dropout
         ctx.dim_origin = d
+        _save_values_version(ctx, graph.val)
         return out
 
     @staticmethod
+    @first_order_only
     def backward(ctx, grad_out):
         saved = ctx.saved_tensors
         sp_index = saved[0]
         grad_x = None
         if ctx.needs_input_grad[0]:
+            _check_values_version(ctx)
             grad_sp = ctx.plan.backward(grad_out.contiguous(), sp_index)
             if len(saved) == 2:
                 grad_sp, sp_index = _mask_padding(grad_sp, sp_index, saved[1])
@@ -394,10 +455,12 @@ class MaxKSelfAggregateFunction(torch.autograd.Function):
         ctx.plan = plan
         ctx.dropout = dropout
         ctx.dim_origin = d
+        _save_values_version(ctx, graph.val)
         ctx.set_materialize_grads(False)  # an unused output arrives as None, not as zeros
         return x_m, out
 
     @staticmethod
+    @first_order_only
     def backward(ctx, g_self, g_agg):
         saved = ctx.saved_tensors
         sp_index = saved[0]
@@ -405,6 +468,7 @@ class MaxKSelfAggregateFunction(torch.autograd.Function):
             return None, None, None, None, None
         grad_sp = None
         if g_agg is not None:
+            _check_values_version(ctx)
             grad_sp = ctx.plan.backward(g_agg.contiguous(), sp_index)
         if len(saved) == 2:
             # a padding slot repeats the last filled slot's selector and gradient, so the last
@@ -478,6 +542,7 @@ class EdgeWeightedFunction(torch.autograd.Function):
         return (x_m, out) if form == "self" else out
 
     @staticmethod
+    @first_order_only
     def backward(ctx, *grads):
         none = (None,) * 7
         g_agg = grads[-1]
@@ -496,7 +561,7 @@ class EdgeWeightedFunction(torch.autograd.Function):
         if ctx.needs_input_grad[0] and (g_agg is not None or g_self is not None):
             grad_sp = None
             if g_agg is not None:
-                if plan._refs[2] is not val or plan.val_version != val._version:
+                if plan._refs[2] is not val or plan.val_version != ops._version(val):
                     plan.refresh_values(val)  # another weighted call ran on this graph since
                 grad_sp = plan.backward(g_agg, sp_index)
             if ctx.form == "spgemm":
@@ -532,15 +597,17 @@ class DenseEdgeWeightedFunction(torch.autograd.Function):
         return ops.dense_spmm(graph.ptr, graph.idx, val, x)
 
     @staticmethod
+    @first_order_only
     def backward(ctx, grad_out):
-        val, graph = ctx.saved_tensors[0], ctx.graph
+        saved, graph = ctx.saved_tensors, ctx.graph   # read once (checkpoint unpacks per read)
+        val = saved[0]
         grad_out = grad_out.contiguous()
         grad_x = grad_val = None
         if ctx.needs_input_grad[0]:
             ptr_t, idx_t, order = graph.transposed_structure()
             grad_x = ops.dense_spmm(ptr_t, idx_t, val[order], grad_out)
         if ctx.needs_input_grad[1]:
-            x = ctx.saved_tensors[1]
+            x = saved[1]
             n, d = x.shape
             ident = torch.arange(d, dtype=torch.uint8, device=x.device).repeat(n, 1)
             grad_val = ops.spgemm_edge_grad(graph.ptr, graph.idx, grad_out, x, ident, n,
@@ -562,6 +629,7 @@ class EdgeSoftmaxFunction(torch.autograd.Function):
         return y
 
     @staticmethod
+    @first_order_only
     def backward(ctx, grad_y):
         if grad_y is None or not ctx.needs_input_grad[1]:
             return None, None

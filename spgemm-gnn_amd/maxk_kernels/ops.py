@@ -46,6 +46,18 @@ def _device(dev: torch.device):
     return _SAME_DEVICE if dev.index == torch.cuda.current_device() else torch.cuda.device(dev)
 
 
+def _version(t: Optional[torch.Tensor]) -> int:
+    """``t._version``, or 0 for a tensor made under ``torch.inference_mode()``: such a tensor
+    tracks no version counter (reading it raises) and cannot be edited in place outside
+    inference mode, so there is no edit to see."""
+    if t is None:
+        return -1
+    try:
+        return t._version
+    except RuntimeError:  # "Inference tensors do not track version counter."
+        return 0
+
+
 def _need(cond: bool, msg: str) -> None:
     if not cond:
         raise RuntimeError(msg)
@@ -329,7 +341,7 @@ class GraphPlan:
         self.handle = ctypes.c_void_p(0)
         self.device = ptr.device
         self._refs = (ptr, idx, val)  # keep the graph's storage alive while cached
-        self.val_version = val._version if val is not None else -1
+        self.val_version = _version(val)
         self.num_rows = int(num_nodes)
         self.num_cols = int(num_nodes if num_cols is None else num_cols)
         self.num_edges = int(num_edges)
@@ -513,7 +525,7 @@ class GraphPlan:
             self._refresh = (stream, ev)
             self._uses[stream.cuda_stream] = stream
         self._refs = (self._refs[0], self._refs[1], val)
-        self.val_version = val._version
+        self.val_version = _version(val)
 
     def info(self) -> dict:
         info = PlanInfo()
@@ -602,13 +614,13 @@ def get_plan(ptr, idx, val, num_nodes, num_edges, dim_origin, dim_k) -> GraphPla
     through a raw pointer, the cached plan of the old structure or values keeps being served.
     Call :func:`clear_plan_cache` after such an edit, or edit the tensor itself
     (``idx.copy_(...)``, ``val.mul_(...)``)."""
-    key = (ptr.device.index, ptr.data_ptr(), idx.data_ptr(), ptr._version, idx._version,
+    key = (ptr.device.index, ptr.data_ptr(), idx.data_ptr(), _version(ptr), _version(idx),
            val.data_ptr(), int(num_nodes), int(num_edges), int(dim_origin), int(dim_k))
     with _PLAN_LOCK:
         plan = _PLAN_CACHE.get(key)
         if plan is not None:
             _PLAN_CACHE.move_to_end(key)
-            if plan._refs[2] is not val or plan.val_version != val._version:
+            if plan._refs[2] is not val or plan.val_version != _version(val):
                 plan.refresh_values(val)
             return plan
         plan = GraphPlan(ptr, idx, val, int(num_nodes), int(num_edges), int(dim_origin),

@@ -45,6 +45,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import ops
+from .autograd import first_order_only
 
 _NS = "maxk"
 
@@ -123,13 +124,16 @@ def _spgemm_setup(ctx, inputs, output):
     ctx.dims = (num_nodes, num_edges, dim_k, dim_origin)
 
 
+@first_order_only
 def _spgemm_backward(ctx, grad):
-    ptr, idx, val, sp_index = ctx.saved_tensors[:4]
+    saved = ctx.saved_tensors  # read once (checkpoint unpacks per read)
+    ptr, idx, val, sp_index = saved[:4]
     grad = grad.contiguous()
-    grad_sp = torch.ops.maxk.spgemm_backward(ptr, idx, val, grad, sp_index, *ctx.dims)
-    grad_val = None
+    grad_sp = grad_val = None
+    if ctx.needs_input_grad[3]:  # no SSpMM for a constant table (only val needs a gradient)
+        grad_sp = torch.ops.maxk.spgemm_backward(ptr, idx, val, grad, sp_index, *ctx.dims)
     if ctx.needs_input_grad[2]:
-        grad_val = torch.ops.maxk.spgemm_edge_grad(ptr, idx, grad, ctx.saved_tensors[4], sp_index,
+        grad_val = torch.ops.maxk.spgemm_edge_grad(ptr, idx, grad, saved[4], sp_index,
                                                    *ctx.dims)
     return None, None, grad_val, grad_sp, None, None, None, None, None
 
@@ -165,6 +169,7 @@ def _edge_softmax_setup(ctx, inputs, output):
     ctx.save_for_backward(inputs[0], output)  # the output only: the backward reads no logits
 
 
+@first_order_only
 def _edge_softmax_backward(ctx, grad):
     ptr, y = ctx.saved_tensors
     return None, torch.ops.maxk.edge_softmax_backward(ptr, y, grad.contiguous())
@@ -178,6 +183,7 @@ def _maxk_setup(ctx, inputs, output):
     ctx.dim_origin = inputs[0].shape[1]
 
 
+@first_order_only
 def _maxk_backward(ctx, grad_data, grad_index):
     (sp_index,) = ctx.saved_tensors
     if grad_data is None:
@@ -221,6 +227,7 @@ def _maxk_dropout_setup(ctx, inputs, output):
     ctx.dropout = (inputs[2], inputs[3])
 
 
+@first_order_only
 def _maxk_dropout_backward(ctx, grad_data, grad_index):
     (sp_index,) = ctx.saved_tensors
     if grad_data is None:
@@ -274,6 +281,7 @@ def _maxk_dense_setup(ctx, inputs, output):
     ctx.set_materialize_grads(False)  # an unused output arrives as None, not as zeros
 
 
+@first_order_only
 def _maxk_dense_backward(ctx, grad_dense, grad_data, grad_index):
     (sp_index,) = ctx.saved_tensors
     if grad_dense is None and grad_data is None:
