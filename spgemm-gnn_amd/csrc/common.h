@@ -211,6 +211,17 @@ struct maxk_plan {
   maxk::DeviceBuf<int32_t> fwd_phase_off;  // [tasks][phases + 1] edge offsets per window
   maxk::DeviceBuf<int32_t> fwd_perm;  // CSR edge id of each permuted forward edge
   maxk::DeviceBuf<uint2> fwd_cv;  // {column | (row within the task << kFwdColBits), val bits}
+  // Row-constant edge values (every edge of a destination row carries the same finite nonzero
+  // value, bit for bit: SAGE mean, sum / GIN, any row-normalised adjacency): fwd_cv4 holds the
+  // column | row words alone, [E + 1] in the same order, fwd_rowval [N] the row's value (1 for
+  // an edgeless row), fwd_cv is released and fwd_fix is computed for unit weights. The
+  // fixed-point forward then sums x with weight 1 and scales each row sum once (its f64 fallback
+  // weighs each term with fwd_rowval of the word's row). Detected at plan build and at every
+  // maxk_plan_refresh_values, which switches the stream either way (plan.hip).
+  int32_t fwd_rowconst = 0;
+  int32_t fwd_rowconst_off = 0;  // maxk_plan_options.fwd_rowconst == 2: always the 8-byte words
+  maxk::DeviceBuf<uint32_t> fwd_cv4;
+  maxk::DeviceBuf<float> fwd_rowval;
   int32_t n_fwd_tasks = 0;
   maxk::DeviceBuf<int32_t> zero_rows;  // rows written by split tasks (atomic), zeroed first
   int32_t n_zero_rows = 0;
@@ -275,6 +286,15 @@ struct maxk_plan {
   int32_t fwd_handout = 1;
   int32_t bwd_handout = 1;
 };
+
+// Whether the plan's forward kernel has a 4-byte edge-word form: the quad-shared windows of 8
+// sub-steps (launch_spgemm_fwd picks the same kernels).
+inline bool plan_fwd_rowconst_shape(const maxk_plan* p) {
+  const int k = p->dim_k;
+  if (!(k % 4 == 0 || p->fwd_chunk3 || p->fwd_chunk2)) return false;
+  const int Lf = p->fwd_chunk3 ? (k + 2) / 3 : p->fwd_chunk2 ? k / 2 : k / 4;  // lanes per edge
+  return p->fwd_quad && Lf % 4 == 0 && p->fwd_unroll == 8 && p->fwd_fix;
+}
 
 // maxk_plan_info.fwd_layout: what the plan's forward gathers from (maxk_hip.h).
 inline int plan_fwd_layout(const maxk_plan* p) {

@@ -153,6 +153,45 @@ __global__ void fwd_fix_stats_kernel(const FwdTask* __restrict__ tasks, int ntas
   out[t] = r;
 }
 
+// Row-constant edge values (common.h, fwd_rowconst): one wavefront per row compares the bits of
+// the row's values with its first one and writes that value to rowval (1 for an edgeless row).
+// *bad is set when a row's values differ or its value is zero or not finite: a row sum scaled
+// once would then put 0 * Inf and the like elsewhere than the per-edge products do.
+__global__ __launch_bounds__(256) void fwd_rowconst_kernel(const int32_t* __restrict__ ptr,
+                                                           const float* __restrict__ val, int N,
+                                                           float* __restrict__ rowval,
+                                                           int* __restrict__ bad) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int r = blockIdx.x * (256 / kWave) + threadIdx.x / kWave;
+  if (r >= N) return;
+  const int e0 = ptr[r], e1 = ptr[r + 1];
+  const uint32_t first = __float_as_uint(e0 < e1 && val ? val[e0] : 1.0f);
+  bool diff = (first & 0x7fffffffu) == 0u || (first & 0x7f800000u) == 0x7f800000u;
+  if (val)
+    for (int e = e0 + lane; e < e1; e += kWave) diff = diff || __float_as_uint(val[e]) != first;
+  if (diff) atomicOr(bad, 1);
+  if (lane == 0) rowval[r] = __uint_as_float(first);
+}
+
+// fwd_cv -> fwd_cv4 (the words without their values; n = E + 1 with the word past the end)
+__global__ void fwd_cv_narrow_kernel(const uint2* __restrict__ cv, int64_t n,
+                                     uint32_t* __restrict__ cv4) {
+  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n;
+       j += (int64_t)gridDim.x * blockDim.x)
+    cv4[j] = cv[j].x;
+}
+
+// fwd_cv4 -> fwd_cv with the values of the CSR order through perm; word E stays zero
+__global__ void fwd_cv_widen_kernel(const uint32_t* __restrict__ cv4,
+                                    const int32_t* __restrict__ perm,
+                                    const float* __restrict__ val, int64_t E,
+                                    uint2* __restrict__ cv) {
+  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j <= E;
+       j += (int64_t)gridDim.x * blockDim.x)
+    cv[j] = j < E ? make_uint2(cv4[j], __float_as_uint(val ? val[perm[j]] : 1.0f))
+                  : make_uint2(0u, 0u);
+}
+
 // Row sums, then per-task bounds (plan create and maxk_plan_refresh_values).
 static hipError_t fwd_fix_stats(const maxk_plan* p, const int32_t* ptr, const float* val,
                                 hipStream_t s) {
@@ -361,6 +400,83 @@ template <class T>
 static void plan_adopt(maxk_plan* p, DeviceBuf<T>& a, DeviceBuf<T>&& scratch) {
   a = std::move(scratch);
   p->device_bytes += (int64_t)a.bytes();
+}
+// An array the plan gives up (the forward's edge stream changing its form at a value refresh).
+template <class T>
+static void plan_release(maxk_plan* p, DeviceBuf<T>& a) {
+  p->device_bytes -= (int64_t)a.bytes();
+  a.reset();
+}
+
+// The forward's edge values: picks the 4-byte stream when the plan's kernel has that form and
+// `val` is row-constant (fwd_rowconst_kernel), else the 8-byte words, converting the stream the
+// plan holds when the answer changed (the words themselves never change: fwd_cv4[j] ==
+// fwd_cv[j].x), and recomputes the fixed-point bounds, for unit weights in the 4-byte form
+// (sum |val| of a row is then its edge count). fresh: fwd_cv already holds `val` (plan build).
+// Reads the detection flag back, so it synchronises the stream where the 4-byte form is possible.
+static hipError_t fwd_set_values(maxk_plan* p, const int32_t* ptr, const float* val, bool fresh,
+                                 hipStream_t s) {
+#define FSV_TRY(expr)                       \
+  do {                                      \
+    const hipError_t _e = (expr);           \
+    if (_e != hipSuccess) return _e;        \
+  } while (0)
+  const int64_t E = p->num_edges;
+  const int N = p->num_nodes;
+  if (E == 0 || !p->fwd_perm) return hipSuccess;
+  const int g = grid_for(E + 1, 256);
+  bool rc = false;
+  DeviceBuf<float> rv;  // the row values of a plan that holds none yet
+  if (!p->fwd_rowconst_off && plan_fwd_rowconst_shape(p) && ptr) {
+    float* dst = p->fwd_rowval;
+    if (!dst) {
+      FSV_TRY(rv.alloc((size_t)N));
+      dst = rv;
+    }
+    int* d_bad = nullptr;  // stream-ordered scratch, as fwd_fix_stats' row sums
+    int bad = 1;
+    FSV_TRY(hipMallocAsync(reinterpret_cast<void**>(&d_bad), sizeof(int), s));
+    hipError_t e = hipMemsetAsync(d_bad, 0, sizeof(int), s);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(fwd_rowconst_kernel, dim3((N + 3) / 4), dim3(256), 0, s, ptr, val, N, dst,
+                         d_bad);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s);
+    const hipError_t f = hipFreeAsync(d_bad, s);
+    FSV_TRY(e);
+    FSV_TRY(f);
+    FSV_TRY(hipStreamSynchronize(s));
+    rc = bad == 0;
+  }
+  if (rc) {
+    if (!p->fwd_cv4) {
+      FSV_TRY(plan_alloc(p, p->fwd_cv4, (size_t)E + 1, true));
+      hipLaunchKernelGGL(fwd_cv_narrow_kernel, dim3(g), dim3(256), 0, s, p->fwd_cv, E + 1,
+                         p->fwd_cv4);
+      FSV_TRY(hipGetLastError());
+      FSV_TRY(hipStreamSynchronize(s));
+      plan_release(p, p->fwd_cv);
+    }
+    if (rv) plan_adopt(p, p->fwd_rowval, std::move(rv));
+  } else if (p->fwd_cv4) {
+    FSV_TRY(plan_alloc(p, p->fwd_cv, (size_t)E + 1, true));
+    hipLaunchKernelGGL(fwd_cv_widen_kernel, dim3(g), dim3(256), 0, s, p->fwd_cv4, p->fwd_perm, val,
+                       E, p->fwd_cv);
+    FSV_TRY(hipGetLastError());
+    FSV_TRY(hipStreamSynchronize(s));
+    plan_release(p, p->fwd_cv4);
+    plan_release(p, p->fwd_rowval);
+  } else if (!fresh) {
+    hipLaunchKernelGGL(gather_fwd_kernel, dim3(grid_for(E, 256)), dim3(256), 0, s, p->fwd_perm,
+                       nullptr, nullptr, val, E, p->fwd_cv, false);
+    FSV_TRY(hipGetLastError());
+  }
+  p->fwd_rowconst = rc ? 1 : 0;
+  if (p->fwd_fix && p->n_fwd_tasks > 0 && (!fresh || rc))
+    FSV_TRY(fwd_fix_stats(p, p->fwd_rowptr, rc ? nullptr : val, s));
+#undef FSV_TRY
+  return hipSuccess;
 }
 
 // Host vector -> device buffer on the stream. The copy is asynchronous: `v` must outlive it, so
@@ -606,6 +722,8 @@ static int check_options(const maxk_plan_options& o) {
   MAXK_CHECK_REMOVED(o.col_order != 3, "col_order = 3 (clustered)");
   MAXK_CHECK_ARG(o.bwd_row_order >= 0 && o.bwd_row_order <= 2,
                  "maxk_plan_create: bwd_row_order must be 0, 1 or 2");
+  MAXK_CHECK_ARG(o.fwd_rowconst >= 0 && o.fwd_rowconst <= 2,
+                 "maxk_plan_create: fwd_rowconst must be 0, 1 or 2");
   return MAXK_OK;
 }
 
@@ -985,6 +1103,9 @@ static int build_forward(PlanBuild& ctx) {
     hipLaunchKernelGGL(fwd_phase_kernel, dim3((nt * (B + 1) + 255) / 256), dim3(256), 0, s,
                        p->fwd_tasks, nt, p->fwd_cv, NC, B, p->fwd_phase_off);
     PLAN_TRY(hipGetLastError());
+    // row-constant values: the 4-byte stream replaces the words just built
+    p->fwd_rowconst_off = o.fwd_rowconst == 2;
+    PLAN_TRY(fwd_set_values(p, p->fwd_rowptr, ctx.val, true, s));
   }
   if (!zrows.empty()) {
     PLAN_TRY(plan_alloc(p, p->zero_rows, zrows.size()));
@@ -1627,17 +1748,21 @@ extern "C" int maxk_plan_refresh_values(maxk_plan* p, const float* val, void* st
     hipLaunchKernelGGL(build_bwd_rec_kernel, dim3(g), dim3(256), 0, s, p->bwd_perm, nullptr,
                        nullptr, val, p->num_edges, p->bwd_block_cols, p->dim_origin, p->bwd_big,
                        p->bwd_rec);
-  if (p->fwd_perm)
-    hipLaunchKernelGGL(gather_fwd_kernel, dim3(g), dim3(256), 0, s, p->fwd_perm, nullptr, nullptr,
-                       val, p->num_edges, p->fwd_cv, false);
-  if (p->fwd_fix && p->n_fwd_tasks > 0) {
-    const hipError_t e = fwd_fix_stats(p, p->fwd_rowptr, val, s);
+  {
+    // the forward's words or row values and its fixed-point bounds; the stream may change form
+    const hipError_t e = fwd_set_values(p, p->fwd_rowptr, val, false, s);
     if (e != hipSuccess) {
       set_error(std::string("maxk_plan_refresh_values: ") + hipGetErrorString(e));
       return (int)e;
     }
   }
   MAXK_LAUNCH_CHECK("maxk_plan_refresh_values launch");
+  return MAXK_OK;
+}
+
+extern "C" int maxk_plan_fwd_rowconst(const maxk_plan* p, int32_t* rowconst) {
+  MAXK_CHECK_ARG(p != nullptr && rowconst != nullptr, "maxk_plan_fwd_rowconst: null pointer");
+  *rowconst = p->fwd_rowconst;
   return MAXK_OK;
 }
 

@@ -338,18 +338,25 @@ __global__ void pack_cbsr3_kernel(const float* __restrict__ sp_data,
 // DPP hands it to the quad: one edge-word instruction per four sub-steps.
 // (Batching the selector words the same way, 64 scattered records per instruction, ran k = 16
 // 1.10 -> 1.48 ms: only contiguous loads gain from fewer instructions.)
-template <class A, int FL, int U>
+// RC (plan->fwd_rowconst; quad windows of U = 8 only): cv is the 4-byte stream fwd_cv4 (the
+// same words without their values). Fixed point: every term has weight 1 and the kernel scales
+// the row sums by fwd_rowval at the write-back. f64 (the per-call fallback): an edge's weight is
+// its row's value, rowval[row of the word] (rowval points at the task's first row), so the
+// terms, and the output bits, are those of the 8-byte words.
+template <class A, int FL, int U, bool RC>
 __device__ __forceinline__ void fwd_edges4(typename A::T* acc, int e0, int e1, int* ctr,
                                            int wave, int nwaves, int EPS, int slot, int l0,
                                            bool lane_on,
-                                           const uint2* __restrict__ cv,
+                                           const void* __restrict__ cvp,
                                            const uint8_t* __restrict__ rec, int rec_bytes,
                                            const uint8_t* __restrict__ seltab, int ss, int D,
-                                           int k, double sc) {
+                                           int k, double sc, const float* __restrict__ rowval) {
   using T = typename A::T;
   constexpr bool C3 = (FL & kFwdFlagChunk3) != 0;
   constexpr bool C2 = (FL & kFwdFlagChunk2) != 0;
   constexpr bool EM = (FL & kFwdFlagQuad) != 0;
+  static_assert(!RC || (EM && U == 8), "4-byte edge words: quad windows of 8 sub-steps");
+  const uint2* cv = static_cast<const uint2*>(cvp);
   const int last = e1 - 1;
   const int qq = threadIdx.x & 3;
   // window i of this wave: wave + i * nwaves (static), or (ctr != nullptr: plan->fwd_handout
@@ -366,7 +373,21 @@ __device__ __forceinline__ void fwd_edges4(typename A::T* acc, int e0, int e1, i
     uint32_t cw[U];
     float v[U];
     bool ok[U];
-    if constexpr (EM && U == 8) {
+    if constexpr (RC) {
+      // eight sub-steps per quad from one 8-B load per lane (two 4-byte edge words, lane q:
+      // sub-steps 2q, 2q + 1); windows and masking as below (fwd_cv4 holds E + 1 words too)
+      const int sb = base + slot * U;
+      const uint2 wq =
+          *reinterpret_cast<const uint2*>(static_cast<const uint32_t*>(cvp) + min(sb + 2 * qq, last & ~1));
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const uint32_t w0 = quad_pick((u & 1) ? wq.y : wq.x, u >> 1);
+        ok[u] = lane_on && sb + u >= e0 && sb + u < e1;
+        cw[u] = ok[u] ? w0 : (w0 & kFwdColMask);
+        if constexpr (A::kFixed) v[u] = 1.0f;
+        else v[u] = rowval[cw[u] >> kFwdColBits];  // a masked word reads the task's row 0
+      }
+    } else if constexpr (EM && U == 8) {
       // eight sub-steps per quad from one 16-B load per lane (two edge words, lane q: sub-steps
       // 2q, 2q + 1). Windows start at even edges (from e0 rounded down; cv holds E + 1 words,
       // so the pair at the last edge stays in bounds); words outside [e0, e1) are masked, with
@@ -458,14 +479,21 @@ __device__ __forceinline__ void fwd_edges4(typename A::T* acc, int e0, int e1, i
 // reuse). accum: the rows of out hold a prior sum to add to (the multi-GPU split's remote
 // part). VEC == 1: k % 4 != 0 beyond the lane chunks' range (k > 192), min(k, 64) lanes per
 // edge looping over the row's k entries, f64 atomics.
-template <int VEC, int FL, int NT, int FU>
+// RC: 4-byte edge words (fwd_edges4). A fixed-point task sums with unit weights and rowval[row]
+// scales the decoded f64 row sum before its one rounding to f32 (each segment's sum of a split
+// row before its atomic add; a continuing launch adds the prior f32 row after that, as every
+// fixed-point task does). An f64 task weighs each term with its row's value and writes back as
+// with the 8-byte words.
+template <int VEC, int FL, int NT, int FU, bool RC>
 __global__ __launch_bounds__(NT) void spgemm_fwd_kernel(
     const FwdTask* __restrict__ tasks, const int32_t* __restrict__ phase_off, int phases,
-    const uint2* __restrict__ cv, const float* __restrict__ sp_data,
+    const void* __restrict__ cv, const float* __restrict__ sp_data,
     const uint8_t* __restrict__ sp_index, const uint8_t* __restrict__ rec, int rec_bytes,
     float* __restrict__ out, int D, int k, int rot_ticks, const uint8_t* __restrict__ seltab,
     int ss, int ds, int accum, const int2* __restrict__ fix_tab,
-    const uint32_t* __restrict__ xstat, int xs_n, int xs_stride, int xs_off2, int handout) {
+    const uint32_t* __restrict__ xstat, int xs_n, int xs_stride, int xs_off2, int handout,
+    const float* __restrict__ rowval) {
+  static_assert(!RC || VEC == 4, "4-byte edge words: the 4-features-per-lane kernels");
   extern __shared__ __align__(16) double smem_d[];
   double* acc = smem_d;
   unsigned long long* acc64 = reinterpret_cast<unsigned long long*>(smem_d);
@@ -528,13 +556,13 @@ __global__ __launch_bounds__(NT) void spgemm_fwd_kernel(
       int* c0 = handout ? &s_win[0] : nullptr;
       int* c1 = handout ? &s_win[1] : nullptr;
       if (emid >= 0) {
-        fwd_edges4<AA, FL, FU>(a, emid, t.e1, c0, wave, kWaves, EPS, slot, l0, lane_on, cv, rec,
-                           rec_bytes, seltab, ss, DS, k, fsc);
-        fwd_edges4<AA, FL, FU>(a, t.e0, emid, c1, wave, kWaves, EPS, slot, l0, lane_on, cv, rec,
-                           rec_bytes, seltab, ss, DS, k, fsc);
+        fwd_edges4<AA, FL, FU, RC>(a, emid, t.e1, c0, wave, kWaves, EPS, slot, l0, lane_on, cv, rec,
+                           rec_bytes, seltab, ss, DS, k, fsc, RC ? rowval + t.row0 : nullptr);
+        fwd_edges4<AA, FL, FU, RC>(a, t.e0, emid, c1, wave, kWaves, EPS, slot, l0, lane_on, cv, rec,
+                           rec_bytes, seltab, ss, DS, k, fsc, RC ? rowval + t.row0 : nullptr);
       } else {
-        fwd_edges4<AA, FL, FU>(a, t.e0, t.e1, c0, wave, kWaves, EPS, slot, l0, lane_on, cv, rec,
-                           rec_bytes, seltab, ss, DS, k, fsc);
+        fwd_edges4<AA, FL, FU, RC>(a, t.e0, t.e1, c0, wave, kWaves, EPS, slot, l0, lane_on, cv, rec,
+                           rec_bytes, seltab, ss, DS, k, fsc, RC ? rowval + t.row0 : nullptr);
       }
     };
     if (fixed) sweep(acc64, LdsFix{});
@@ -543,7 +571,7 @@ __global__ __launch_bounds__(NT) void spgemm_fwd_kernel(
     for (int base = t.e0 + wave * EPS; base < t.e1; base += kWaves * EPS) {
       const int e = base + slot;
       if (lane_on && e < t.e1) {
-        const uint2 w = cv[e];
+        const uint2 w = static_cast<const uint2*>(cv)[e];
         const float v = __uint_as_float(w.y);
         double* arow = acc + (w.x >> kFwdColBits) * DS;
         const size_t c = w.x & kFwdColMask;
@@ -556,16 +584,25 @@ __global__ __launch_bounds__(NT) void spgemm_fwd_kernel(
 
   float* dst = out + (size_t)t.row0 * D;
   const double finv = fixed ? 1.0 / fsc : 0.0;  // 2^-s, exact
-  auto get = [&](int i) -> float {
+  // rs: the row's value (RC), loaded once per row of a thread's elements
+  auto rowscale = [&](int r) -> double {
+    if constexpr (RC) return (double)rowval[t.row0 + r];
+    return 1.0;
+  };
+  auto get = [&](int i, double rs) -> float {
     const int r = i / D;
-    if (fixed) return (float)fwd_fix_decode(acc64[r * DS + (i - r * D)], finv);
-    return (float)acc[r * DS + (i - r * D)];
+    double a = fixed ? fwd_fix_decode(acc64[r * DS + (i - r * D)], finv) : acc[r * DS + (i - r * D)];
+    if constexpr (RC) {
+      if (fixed) a *= rs;
+    }
+    return (float)a;
   };
   if (!split) {
     const bool add = accum && fixed;  // the prior row is added here (see above)
     if ((D & 3) == 0) {
       for (int i = threadIdx.x * 4; i < n; i += NT * 4) {
-        float4 v = make_float4(get(i), get(i + 1), get(i + 2), get(i + 3));
+        const double rs = rowscale(i / D);  // D % 4 == 0: the four elements share a row
+        float4 v = make_float4(get(i, rs), get(i + 1, rs), get(i + 2, rs), get(i + 3, rs));
         if (add) {
           const float4 o = *reinterpret_cast<const float4*>(dst + i);
           v = make_float4(o.x + v.x, o.y + v.y, o.z + v.z, o.w + v.w);
@@ -573,10 +610,14 @@ __global__ __launch_bounds__(NT) void spgemm_fwd_kernel(
         *reinterpret_cast<float4*>(dst + i) = v;
       }
     } else {
-      for (int i = threadIdx.x; i < n; i += NT) dst[i] = add ? dst[i] + get(i) : get(i);
+      for (int i = threadIdx.x; i < n; i += NT) {
+        const float a = get(i, rowscale(i / D));
+        dst[i] = add ? dst[i] + a : a;
+      }
     }
   } else {
-    for (int i = threadIdx.x; i < D; i += NT) global_add(dst + i, get(i));
+    const double rs = rowscale(0);
+    for (int i = threadIdx.x; i < D; i += NT) global_add(dst + i, get(i, rs));
   }
 }
 
@@ -1247,32 +1288,43 @@ static int launch_spgemm_fwd(const maxk_plan* plan, const float* sp_data, int ds
   const int FL = (plan->fwd_chunk3 ? kFwdFlagChunk3 : 0) | (pairs ? kFwdFlagChunk2 : 0) |
                  (plan->fwd_quad && Lf % 4 == 0 ? kFwdFlagQuad : 0);
   const int fwaves = plan->fwd_waves;
-#define FWD_LAUNCH_NT(V, FF, NT, FU)                                                        \
+  // 4-byte edge words (plan->fwd_rowconst): the quad kernels of 8 sub-steps only
+  const bool rc = plan->fwd_rowconst != 0;
+  if (rc && !plan_fwd_rowconst_shape(plan)) {
+    set_error("spgemm_fwd launch: 4-byte edge words on a plan whose kernel has none");
+    return MAXK_ERR_UNSUPPORTED;
+  }
+  const void* cvp = rc ? static_cast<const void*>(plan->fwd_cv4.get())
+                       : static_cast<const void*>(plan->fwd_cv.get());
+#define FWD_LAUNCH_NT(V, FF, NT, FU, RC)                                                    \
   do {                                                                                      \
-    if (lds > 64 * 1024) MAXK_HIP_TRY(allow_lds(spgemm_fwd_kernel<V, FF, NT, FU>, lds));     \
-    hipLaunchKernelGGL((spgemm_fwd_kernel<V, FF, NT, FU>), dim3(plan->n_fwd_tasks), dim3(NT), \
-                       lds, s, plan->fwd_tasks, plan->fwd_phase_off, plan->fwd_phases,      \
-                       plan->fwd_cv, sp_data, sp_index, recp, rec_bytes, out, D, k,         \
+    if (lds > 64 * 1024) MAXK_HIP_TRY(allow_lds(spgemm_fwd_kernel<V, FF, NT, FU, RC>, lds)); \
+    hipLaunchKernelGGL((spgemm_fwd_kernel<V, FF, NT, FU, RC>), dim3(plan->n_fwd_tasks),     \
+                       dim3(NT), lds, s, plan->fwd_tasks, plan->fwd_phase_off,              \
+                       plan->fwd_phases, cvp, sp_data, sp_index, recp, rec_bytes, out, D, k, \
                        plan->fwd_rot_ticks, seltab, is, ds, accum, fix_tab, xstat, xs_n,     \
-                       xs_stride, xs_off2, plan->fwd_handout == 2 ? 1 : 0);                 \
+                       xs_stride, xs_off2, plan->fwd_handout == 2 ? 1 : 0,                  \
+                       plan->fwd_rowval.get());                                             \
   } while (0)
-#define FWD_LAUNCH(V, FF)                                                                   \
+#define FWD_LAUNCH(V, FF, RCOK) /* RCOK: the variant has a 4-byte kernel (checked above) */ \
   do {                                                                                      \
-    if (fwaves == 8 && plan->fwd_unroll == 4) FWD_LAUNCH_NT(V, FF, 8 * kWave, 4);            \
-    else if (fwaves == 8) FWD_LAUNCH_NT(V, FF, 8 * kWave, kFwdUnroll);                      \
-    else FWD_LAUNCH_NT(V, FF, kFwdThreads, kFwdUnroll);                                     \
+    if (rc && fwaves == 8) FWD_LAUNCH_NT(V, FF, 8 * kWave, kFwdUnroll, RCOK);               \
+    else if (rc) FWD_LAUNCH_NT(V, FF, kFwdThreads, kFwdUnroll, RCOK);                       \
+    else if (fwaves == 8 && plan->fwd_unroll == 4) FWD_LAUNCH_NT(V, FF, 8 * kWave, 4, false); \
+    else if (fwaves == 8) FWD_LAUNCH_NT(V, FF, 8 * kWave, kFwdUnroll, false);               \
+    else FWD_LAUNCH_NT(V, FF, kFwdThreads, kFwdUnroll, false);                              \
   } while (0)
   if (k % 4 == 0 || plan->fwd_chunk3 || plan->fwd_chunk2) {
     switch (FL) {
-      case 0: FWD_LAUNCH(4, 0); break;
-      case kFwdFlagChunk3: FWD_LAUNCH(4, kFwdFlagChunk3); break;
-      case kFwdFlagQuad: FWD_LAUNCH(4, kFwdFlagQuad); break;
-      case kFwdFlagChunk2: FWD_LAUNCH(4, kFwdFlagChunk2); break;
-      case kFwdFlagChunk2 | kFwdFlagQuad: FWD_LAUNCH(4, kFwdFlagChunk2 | kFwdFlagQuad); break;
-      default: FWD_LAUNCH(4, kFwdFlagChunk3 | kFwdFlagQuad); break;
+      case 0: FWD_LAUNCH(4, 0, false); break;
+      case kFwdFlagChunk3: FWD_LAUNCH(4, kFwdFlagChunk3, false); break;
+      case kFwdFlagQuad: FWD_LAUNCH(4, kFwdFlagQuad, true); break;
+      case kFwdFlagChunk2: FWD_LAUNCH(4, kFwdFlagChunk2, false); break;
+      case kFwdFlagChunk2 | kFwdFlagQuad: FWD_LAUNCH(4, kFwdFlagChunk2 | kFwdFlagQuad, true); break;
+      default: FWD_LAUNCH(4, kFwdFlagChunk3 | kFwdFlagQuad, true); break;
     }
   } else {
-    FWD_LAUNCH(1, 0);
+    FWD_LAUNCH(1, 0, false);
   }
 #undef FWD_LAUNCH
 #undef FWD_LAUNCH_NT

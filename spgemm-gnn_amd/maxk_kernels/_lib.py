@@ -53,6 +53,7 @@ SIGNATURES = {
     "maxk_plan_create_sized": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i64, _i32, _i32,
                                               _vp, _i64, _vp, _vp, ctypes.POINTER(_vp)]),
     "maxk_plan_refresh_values": (ctypes.c_int, [_vp, _vp, _vp]),
+    "maxk_plan_fwd_rowconst": (ctypes.c_int, [_vp, ctypes.POINTER(_i32)]),
     "maxk_plan_get_info": (ctypes.c_int, [_vp, _vp]),
     "maxk_plan_get_info_sized": (ctypes.c_int, [_vp, _vp, _i64]),
     "maxk_plan_get_col_order": (ctypes.c_int, [_vp, _vp, _vp]),
@@ -140,6 +141,8 @@ class PlanOptions(ctypes.Structure):
         # round 5
         ("fwd_handout", _i32),
         ("bwd_handout", _i32),
+        # round 12
+        ("fwd_rowconst", _i32),
     ]
 
 

@@ -501,7 +501,9 @@ class GraphPlan:
 
     def refresh_values(self, val: torch.Tensor) -> None:
         """Re-snapshot in-place-modified edge values (same tensor, new ``_version``); runs
-        after every earlier use of the plan on any stream. It allocates stream-ordered scratch
+        after every earlier use of the plan on any stream. It allocates stream-ordered scratch,
+        tests the new values for row-constancy where the forward has a 4-byte edge-word form
+        (``info()['fwd_rowconst']`` may change; that read-back synchronises the stream)
         and orders itself across streams with events, and a replay would skip its host
         bookkeeping, so it is refused while a graph is being captured (that covers
         ``edge_weight=`` and :func:`get_plan` after an in-place edit of ``val``)."""
@@ -534,6 +536,11 @@ class GraphPlan:
         d = info.as_dict()
         d["fwd_workspace_bytes"] = self.fwd_ws_bytes
         d["bwd_workspace_bytes"] = self.bwd_ws_bytes
+        # 1: 4-byte forward edge words and one value per row (the values of the last build or
+        # refresh were row-constant); changes with refresh_values, so read every time
+        rc = ctypes.c_int32(0)
+        check(lib.maxk_plan_fwd_rowconst(self.handle, ctypes.byref(rc)), "maxk_plan_fwd_rowconst")
+        d["fwd_rowconst"] = int(rc.value)
         return d
 
     @property

@@ -32,11 +32,13 @@ def main():
     ap.add_argument("--dataset", default="reddit")
     ap.add_argument("--opts", default='[{}]')
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--values", default="sage", choices=("sage", "gcn"),
+                    help="edge values: SAGE mean (constant per row) or GCN (not)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     n, e = graphs.DATASETS[args.dataset]
     ptr, idx = graphs.bench_csr(args.dataset, device=dev)
-    val = graphs.sage_mean_values(ptr)
+    val = graphs.sage_mean_values(ptr) if args.values == "sage" else graphs.gcn_values(ptr, idx)
     e = idx.numel()
     h = graphs.features(n, 256, seed=97, device=dev)
     sd, si = mk.maxk_forward(h, args.k, return_index=True)
@@ -50,7 +52,8 @@ def main():
     for i, opts in enumerate(sets):
         t = sorted(times[i])
         dev_max = float(((outs[i] - outs[0]).abs() / (outs[0].abs() + 1e-3)).max())
-        print(json.dumps({"k": args.k, "opts": opts, "fwd_ms": round(t[len(t) // 2], 4),
+        print(json.dumps({"k": args.k, "values": args.values,
+                          "fwd_rowconst": plans[i].info().get("fwd_rowconst", 0), "opts": opts, "fwd_ms": round(t[len(t) // 2], 4),
                           "fwd_ms_all": [round(x, 4) for x in times[i]],
                           "tasks": plans[i].info()["fwd_tasks"], "max_rel_dev": dev_max}),
               flush=True)

@@ -114,7 +114,7 @@ void digest(const char* name, const Graph& g, int32_t D, int32_t k, const maxk_p
   S(num_nodes); S(num_cols); S(num_edges); S(dim_origin); S(dim_k); S(cus);
   S(fwd_tile_rows); S(fwd_waves); S(fwd_unroll); S(fwd_rec_bytes); S(fwd_fixed); S(fwd_xstat_off);
   S(fwd_phases); S(fwd_rot_ticks); S(fwd_chunk3); S(fwd_chunk2); S(fwd_quad); S(fwd_two_tables);
-  S(n_fwd_tasks); S(n_zero_rows);
+  S(n_fwd_tasks); S(n_zero_rows); S(fwd_rowconst);
   S(bwd_feats); S(bwd_slot_groups); S(bwd_kp); S(bwd_ks); S(bwd_unroll); S(bwd_waves); S(bwd_big);
   S(bwd_block_cols); S(n_bwd_blocks); S(n_bwd_tasks); S(n_bwd_shared);
   S(bwd_twopass); S(bwd_tp_rows); S(bwd_tp_chunks); S(col_order);
@@ -131,6 +131,8 @@ void digest(const char* name, const Graph& g, int32_t D, int32_t k, const maxk_p
   array_line("fwd_rec", p->fwd_rec, 0, 0);
   array_line("fwd_perm", p->fwd_perm, E, 4);
   array_line("fwd_cv", p->fwd_cv, E + 1, 8);
+  array_line("fwd_cv4", p->fwd_cv4, E + 1, 4);
+  array_line("fwd_rowval", p->fwd_rowval, (int64_t)g.N, 4);
   array_line("fwd_fix", p->fwd_fix, nt, 8);
   array_line("fwd_rowptr", p->fwd_rowptr, (int64_t)g.N + 1, 4);
   array_line("fwd_phase_off", p->fwd_phase_off, nt * (p->fwd_phases + 1), 4);
