@@ -25,83 +25,16 @@
 // segment's alignment and num_rows never enter, so a row's bits depend on its values and length.
 // Loads are one dword per lane, 64 contiguous lanes: vector loads would tie the order to
 // ptr[r] % 4.
-#include "common.h"
+// The device functions are shared with gat_attention.hip (edge_softmax.h): here their source is
+// the logits array.
+#include "edge_softmax.h"
 
 // every product, difference and sum below is one IEEE operation
 #pragma clang fp contract(off)
 
 namespace maxk {
 
-constexpr int kEsThreads = 256;
-constexpr int kEsWaves = kEsThreads / kWave;
-constexpr int kEsGroup = 16;                           // lanes of a short row
-constexpr int kEsWaveRows = kWave / kEsGroup;          // rows of a wave
-constexpr int kEsTileRows = kEsWaves * kEsWaveRows;    // rows of a work-group
-constexpr int kEsShortSlots = 4;
-constexpr int kEsShortMax = kEsGroup * kEsShortSlots;  // 64
-constexpr int kEsMediumSlots = 16;
-constexpr int kEsMediumMax = kWave * kEsMediumSlots;   // 1024
-constexpr int kEsHubUnroll = 4;
-
-template <int W>
-__device__ __forceinline__ float es_max(float v) {
-#pragma unroll
-  for (int m = W / 2; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, kWave));
-  return v;
-}
-
-template <int W>
-__device__ __forceinline__ float es_sum(float v) {
-#pragma unroll
-  for (int m = 1; m < W; m <<= 1) v = v + __shfl_xor(v, m, kWave);
-  return v;
-}
-
-// Segment [b, b + n) of a row, clamped into [0, E] so that a ptr that breaks the documented
-// preconditions still indexes inside the arrays.
-__device__ __forceinline__ void es_segment(const int32_t* __restrict__ ptr, int64_t row,
-                                           int32_t num_rows, int64_t E, int64_t& b, int32_t& n) {
-  b = 0;
-  n = 0;
-  if (row < num_rows) {
-    int64_t lo = ptr[row], hi = ptr[row + 1];
-    lo = lo < 0 ? 0 : (lo > E ? E : lo);
-    hi = hi < lo ? lo : (hi > E ? E : hi);
-    b = lo;
-    n = (int32_t)(hi - lo);
-  }
-}
-
 // ---------------------------------------------------------------------------------- forward
-// W lanes (lane `sub` of them) hold S slots each of the row x[0, n), n in [0, W * S]. Loads are
-// unconditional at a clamped index (`safe`: an in-bounds element for a group with no row), so
-// all S are in flight together.
-template <int W, int S>
-__device__ __forceinline__ void es_fwd_regs(const float* __restrict__ x, float* __restrict__ out,
-                                            int32_t n, int sub) {
-  float v[S];
-  const int32_t last = n > 0 ? n - 1 : 0;
-#pragma unroll
-  for (int i = 0; i < S; ++i) {
-    const int32_t j = sub + W * i;
-    v[i] = x[j < last ? j : last];
-  }
-  float m = -INFINITY;
-#pragma unroll
-  for (int i = 0; i < S; ++i) m = fmaxf(m, sub + W * i < n ? v[i] : -INFINITY);
-  m = es_max<W>(m);
-  float a = 0.f;
-#pragma unroll
-  for (int i = 0; i < S; ++i) {
-    v[i] = sub + W * i < n ? expf(v[i] - m) : 0.f;
-    a = a + v[i];
-  }
-  const float inv = 1.0f / es_sum<W>(a);
-#pragma unroll
-  for (int i = 0; i < S; ++i)
-    if (sub + W * i < n) out[sub + W * i] = v[i] * inv;
-}
-
 __global__ __launch_bounds__(kEsThreads) void edge_softmax_fwd_kernel(
     const int32_t* __restrict__ ptr, const float* __restrict__ logits, float* __restrict__ out,
     int32_t num_rows, int64_t E) {
@@ -118,19 +51,14 @@ __global__ __launch_bounds__(kEsThreads) void edge_softmax_fwd_kernel(
   if (__ballot(ns > 0) != 0) {
     // a group with no short row reads element 0 (E > 0) and writes nothing
     const int64_t bs = ns > 0 ? b : 0;
-    es_fwd_regs<kEsGroup, kEsShortSlots>(logits + bs, out + bs, ns, lane % kEsGroup);
+    es_fwd_regs<kEsGroup, kEsShortSlots>(EsArray{logits + bs}, out + bs, ns, lane % kEsGroup);
   }
 #pragma unroll
   for (int g = 0; g < kEsWaveRows; ++g) {
     const int32_t ng = __shfl(n, g * kEsGroup, kWave);
     if (ng <= kEsShortMax || ng > kEsMediumMax) continue;  // wave-uniform
     const int64_t bg = __shfl(b, g * kEsGroup, kWave);
-    const float* x = logits + bg;
-    float* o = out + bg;
-    if (ng <= 2 * kWave) es_fwd_regs<kWave, 2>(x, o, ng, lane);
-    else if (ng <= 4 * kWave) es_fwd_regs<kWave, 4>(x, o, ng, lane);
-    else if (ng <= 8 * kWave) es_fwd_regs<kWave, 8>(x, o, ng, lane);
-    else es_fwd_regs<kWave, kEsMediumSlots>(x, o, ng, lane);
+    es_fwd_medium(EsArray{logits + bg}, out + bg, ng, lane);
   }
 
   // the tile's hub rows: every thread reads the same lengths, so the branch is group-uniform
@@ -139,52 +67,11 @@ __global__ __launch_bounds__(kEsThreads) void edge_softmax_fwd_kernel(
     int32_t nh;
     es_segment(ptr, row0 + r, num_rows, E, bh, nh);
     if (nh <= kEsMediumMax) continue;
-    const float* x = logits + bh;
-    float* o = out + bh;
-    float m = -INFINITY;
-#pragma unroll kEsHubUnroll
-    for (int32_t j = tid; j < nh; j += kEsThreads) m = fmaxf(m, x[j]);
-    m = es_max<kWave>(m);
-    if (lane == 0) red[wave] = m;
-    __syncthreads();
-    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    float a = 0.f;
-#pragma unroll kEsHubUnroll
-    for (int32_t j = tid; j < nh; j += kEsThreads) a = a + expf(x[j] - m);
-    a = es_sum<kWave>(a);
-    if (lane == 0) red[kEsWaves + wave] = a;
-    __syncthreads();
-    const float inv = 1.0f / ((red[kEsWaves] + red[kEsWaves + 1]) +
-                              (red[kEsWaves + 2] + red[kEsWaves + 3]));
-#pragma unroll kEsHubUnroll
-    for (int32_t j = tid; j < nh; j += kEsThreads) o[j] = expf(x[j] - m) * inv;
-    __syncthreads();  // red is free for the tile's next hub
+    es_fwd_hub(EsArray{logits + bh}, out + bh, nh, tid, lane, wave, red);
   }
 }
-static_assert(kEsWaves == 4, "the hub rows combine four waves");
 
 // --------------------------------------------------------------------------------- backward
-template <int W, int S>
-__device__ __forceinline__ void es_bwd_regs(const float* __restrict__ y,
-                                            const float* __restrict__ gy, float* __restrict__ out,
-                                            int32_t n, int sub) {
-  float v[S], g[S];
-  const int32_t last = n > 0 ? n - 1 : 0;
-#pragma unroll
-  for (int i = 0; i < S; ++i) {
-    const int32_t j = sub + W * i;
-    v[i] = y[j < last ? j : last];
-    g[i] = gy[j < last ? j : last];
-  }
-  float a = 0.f;
-#pragma unroll
-  for (int i = 0; i < S; ++i) a = a + (sub + W * i < n ? v[i] * g[i] : 0.f);
-  const float t = es_sum<W>(a);
-#pragma unroll
-  for (int i = 0; i < S; ++i)
-    if (sub + W * i < n) out[sub + W * i] = v[i] * (g[i] - t);
-}
-
 __global__ __launch_bounds__(kEsThreads) void edge_softmax_bwd_kernel(
     const int32_t* __restrict__ ptr, const float* __restrict__ y, const float* __restrict__ gy,
     float* __restrict__ out, int32_t num_rows, int64_t E) {
@@ -199,17 +86,15 @@ __global__ __launch_bounds__(kEsThreads) void edge_softmax_bwd_kernel(
   const int32_t ns = n <= kEsShortMax ? n : 0;
   if (__ballot(ns > 0) != 0) {
     const int64_t bs = ns > 0 ? b : 0;
-    es_bwd_regs<kEsGroup, kEsShortSlots>(y + bs, gy + bs, out + bs, ns, lane % kEsGroup);
+    es_bwd_regs<kEsGroup, kEsShortSlots>(y + bs, gy + bs, out + bs, ns, lane % kEsGroup,
+                                         EsNoPost{});
   }
 #pragma unroll
   for (int g = 0; g < kEsWaveRows; ++g) {
     const int32_t ng = __shfl(n, g * kEsGroup, kWave);
     if (ng <= kEsShortMax || ng > kEsMediumMax) continue;  // wave-uniform
     const int64_t bg = __shfl(b, g * kEsGroup, kWave);
-    if (ng <= 2 * kWave) es_bwd_regs<kWave, 2>(y + bg, gy + bg, out + bg, ng, lane);
-    else if (ng <= 4 * kWave) es_bwd_regs<kWave, 4>(y + bg, gy + bg, out + bg, ng, lane);
-    else if (ng <= 8 * kWave) es_bwd_regs<kWave, 8>(y + bg, gy + bg, out + bg, ng, lane);
-    else es_bwd_regs<kWave, kEsMediumSlots>(y + bg, gy + bg, out + bg, ng, lane);
+    es_bwd_medium(y + bg, gy + bg, out + bg, ng, lane, EsNoPost{});
   }
 
   for (int r = 0; r < kEsTileRows; ++r) {
@@ -217,18 +102,7 @@ __global__ __launch_bounds__(kEsThreads) void edge_softmax_bwd_kernel(
     int32_t nh;
     es_segment(ptr, row0 + r, num_rows, E, bh, nh);
     if (nh <= kEsMediumMax) continue;
-    const float* yv = y + bh;
-    const float* gv = gy + bh;
-    float* o = out + bh;
-    float a = 0.f;
-#pragma unroll kEsHubUnroll
-    for (int32_t j = tid; j < nh; j += kEsThreads) a = a + yv[j] * gv[j];
-    a = es_sum<kWave>(a);
-    if (lane == 0) red[wave] = a;
-    __syncthreads();
-    const float t = (red[0] + red[1]) + (red[2] + red[3]);
-#pragma unroll kEsHubUnroll
-    for (int32_t j = tid; j < nh; j += kEsThreads) o[j] = yv[j] * (gv[j] - t);
+    es_bwd_hub(y + bh, gy + bh, out + bh, nh, tid, lane, wave, red, EsNoPost{});
     __syncthreads();  // red is free for the tile's next hub
   }
 }
@@ -246,10 +120,6 @@ static int es_check(const std::string& w, const int32_t* ptr, const float* const
   for (int i = 0; i < nin; ++i) overlap = overlap || ranges_overlap(out, 4 * E, ins[i], 4 * E);
   MAXK_CHECK_ARG(!overlap, w + "the output overlaps an input");
   return MAXK_OK;
-}
-
-static dim3 es_grid(int32_t N) {
-  return dim3((unsigned)(((int64_t)N + kEsTileRows - 1) / kEsTileRows));
 }
 
 }  // namespace maxk

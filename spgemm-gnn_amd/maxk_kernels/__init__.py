@@ -50,6 +50,7 @@ from .autograd import (  # noqa: F401
 )
 
 from . import torch_ops  # noqa: F401,E402  (registers torch.ops.maxk.*)
+from .attention import GATAttentionFunction, gat_attention  # noqa: F401,E402  (and its operators)
 from .layers import (  # noqa: F401,E402
     MaxKGCN,
     MaxKGATConv,
@@ -68,7 +69,7 @@ __all__ = [
     "MaxKGIN", "dense_aggregate", "DenseAggFunction", "MaxKSelfAggregateFunction",
     "maxk_self_aggregate", "spgemm_edge_grad", "EdgeWeightedFunction", "DenseEdgeWeightedFunction",
     "edge_softmax", "edge_softmax_backward", "edge_softmax_row_limits", "EdgeSoftmaxFunction",
-    "MaxKGATConv",
+    "MaxKGATConv", "gat_attention", "GATAttentionFunction",
 ]
 
 ABI_VERSION = lib.maxk_abi_version()

@@ -240,6 +240,15 @@ class CSRGraph:
             self._values["transposed_structure"] = st
         return st
 
+    def transposed_order(self) -> torch.Tensor:
+        """``transposed_structure()[2]`` as a contiguous int32 ``[E]`` tensor, cached: the
+        ``order`` of ``ops.edge_colsum`` (half the bytes of the int64 one per gathered edge)."""
+        order = self._values.get("transposed_order")
+        if order is None:
+            order = self.transposed_structure()[2].to(torch.int32).contiguous()
+            self._values["transposed_order"] = order
+        return order
+
     def with_values(self, kind: str) -> "CSRGraph":
         """Same structure with the ``kind`` edge weights (shares ptr/idx, hence the plan)."""
         key = ("graph", kind)

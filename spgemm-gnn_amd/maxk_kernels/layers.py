@@ -76,6 +76,7 @@ import torch.nn.functional as F
 
 from .autograd import (CSRGraph, dense_aggregate, densify, edge_softmax, maxk, maxk_aggregate,
                        maxk_self_aggregate, spgemm)
+from .attention import gat_attention
 
 NONLINEAR = ("maxk", "relu")
 
@@ -268,14 +269,19 @@ class MaxKGATConv(nn.Module):
     aggregation ``maxk_aggregate(..., edge_weight=alpha)`` on the unit-valued graph with the
     ``feat_drop`` / ``fused_dropout`` branches of :class:`MaxKGCNConv`; ``nonlinear="relu"``
     aggregates the dense ``h`` (``dense_aggregate``). The score gather ``el[idx] +
-    er[edge_rows]`` and its gradient are torch's. The attention needs the CSRGraph's own edge
-    order, so a DGL graph raises the ``TypeError`` of ``edge_weight=``."""
+    er[edge_rows]`` and its gradient are torch's; with ``fused_attention=True`` (default off)
+    the gather, add, leaky-relu and softmax are the one kernel of :func:`gat_attention` and the
+    score gradients its two backward kernels: the same ``alpha`` and output bit for bit, no
+    ``[E]`` intermediates, and gradients to ``attn_l``, ``attn_r`` and ``fc`` summed in a fixed
+    order that is another order than ``index_add``'s. The attention needs the CSRGraph's own
+    edge order, so a DGL graph raises the ``TypeError`` of ``edge_weight=``."""
 
     def __init__(self, in_feats, out_feats, maxk=32, negative_slope=0.2, attn_drop=0.,
                  feat_drop=0., bias=True, allow_zero_in_degree=False, topk_mode="exact",
-                 nonlinear="maxk", fused_dropout=False):
+                 nonlinear="maxk", fused_dropout=False, fused_attention=False):
         super().__init__()
         self.fused_dropout = bool(fused_dropout)
+        self.fused_attention = bool(fused_attention)
         self.in_feats = in_feats
         self.out_feats = out_feats
         self.maxk = maxk
@@ -306,8 +312,11 @@ class MaxKGATConv(nn.Module):
         h = self.fc(feat)
         el = (h * self.attn_l).sum(-1)
         er = (h * self.attn_r).sum(-1)
-        e = F.leaky_relu(el[csr.idx] + er[csr.edge_rows()], self.negative_slope)
-        alpha = edge_softmax(csr, e)
+        if self.fused_attention:
+            alpha = gat_attention(csr, el, er, self.negative_slope)
+        else:
+            e = F.leaky_relu(el[csr.idx] + er[csr.edge_rows()], self.negative_slope)
+            alpha = edge_softmax(csr, e)
         if self.attn_drop > 0:
             alpha = F.dropout(alpha, self.attn_drop, self.training)
         g = csr.with_values("sum")

@@ -812,6 +812,94 @@ def edge_softmax_row_limits() -> Tuple[int, ...]:
     return tuple(int(v) for v in buf)
 
 
+def _vector(t, name: str, dtype: torch.dtype, size, size_name: str, dev) -> None:
+    """A contiguous 1-D ``dtype`` tensor of ``size`` entries (``None``: any) on ``dev``."""
+    _check_tensor(t, name, dtype)
+    _need(t.dim() == 1 and (size is None or t.numel() == size), f"{name} must be [{size_name}]")
+    _need(t.device == dev, "all tensors must be on the same device")
+
+
+def _gat_attention_args(ptr, idx, el, er):
+    """The checks shared by :func:`gat_attention` and :func:`gat_attention_backward`: ``ptr``
+    int32 ``[num_rows + 1]``, ``idx`` int32 ``[num_edges]``, ``el`` f32 ``[num_cols]``, ``er`` f32
+    ``[num_rows]`` on ``ptr``'s device. Returns ``(num_rows, num_cols, num_edges)``."""
+    _check_tensor(ptr, "ptr", torch.int32)
+    _need(ptr.dim() == 1 and ptr.numel() >= 1, "ptr must have num_rows+1 entries")
+    dev = ptr.device
+    _vector(idx, "idx", torch.int32, None, "num_edges", dev)
+    _vector(el, "el", torch.float32, None, "num_cols", dev)
+    _vector(er, "er", torch.float32, ptr.numel() - 1, "num_rows", dev)
+    return ptr.numel() - 1, el.numel(), idx.numel()
+
+
+def _out_vector(out, name: str, size: int, size_name: str, dev) -> torch.Tensor:
+    if out is None:
+        return torch.empty(size, dtype=torch.float32, device=dev)
+    _check_tensor(out, name, torch.float32)
+    _need(out.dim() == 1 and out.numel() == size and out.device == dev,
+          f"{name} must be [{size_name}] on the graph's device")
+    return out
+
+
+def gat_attention(ptr, idx, el, er, negative_slope: float,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Attention weights of single-head GAT from the two node score vectors, one kernel: the
+    :func:`edge_softmax` of ``leaky_relu(el[idx] + er[row], negative_slope)`` over each row's
+    in-edges, bit for bit, with no ``[num_edges]`` intermediate (``maxk_gat_attention_forward``;
+    include/maxk_hip.h, "GAT attention"). ``el`` is f32 ``[num_cols]`` (the source side), ``er``
+    f32 ``[num_rows]``; ``idx`` lies in ``[0, num_cols)`` and ``ptr[-1] == num_edges`` (neither is
+    read on the host). ``out``: a contiguous f32 ``[num_edges]`` tensor to write into."""
+    n, c, e = _gat_attention_args(ptr, idx, el, er)
+    out = _out_vector(out, "out", e, "num_edges", ptr.device)
+    with _device(ptr.device):
+        check(lib.maxk_gat_attention_forward(_p(ptr), _p(idx), _p(el), _p(er),
+                                             float(negative_slope), _p(out), n, c, e, _stream()),
+              "gat_attention")
+    return out
+
+
+def gat_attention_backward(ptr, idx, el, er, negative_slope: float, alpha, grad_alpha,
+                           out=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(grad_edge [num_edges], grad_er [num_rows])`` of :func:`gat_attention` from its output
+    ``alpha`` and that output's gradient: ``grad_edge`` is the gradient with respect to the sum
+    ``el[idx] + er[row]`` (the softmax backward through the leaky-relu branch of the recomputed
+    score), ``grad_er`` its sum over each row in a fixed order
+    (``maxk_gat_attention_backward``). ``grad_el`` is :func:`edge_colsum` of ``grad_edge``.
+    ``out=(grad_edge, grad_er)``: contiguous f32 tensors to write into."""
+    n, c, e = _gat_attention_args(ptr, idx, el, er)
+    dev = ptr.device
+    _vector(alpha, "alpha", torch.float32, e, "num_edges", dev)
+    _vector(grad_alpha, "grad_alpha", torch.float32, e, "num_edges", dev)
+    grad_edge, grad_er = out if out is not None else (None, None)
+    grad_edge = _out_vector(grad_edge, "out[0]", e, "num_edges", dev)
+    grad_er = _out_vector(grad_er, "out[1]", n, "num_rows", dev)
+    with _device(dev):
+        check(lib.maxk_gat_attention_backward(_p(ptr), _p(idx), _p(el), _p(er),
+                                              float(negative_slope), _p(alpha), _p(grad_alpha),
+                                              _p(grad_edge), _p(grad_er), n, c, e, _stream()),
+              "gat_attention_backward")
+    return grad_edge, grad_er
+
+
+def edge_colsum(ptr_t, order, values, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Sum of the per-edge ``values`` (f32 ``[num_edges]``, CSR edge order) over each source
+    column, f32 ``[num_cols]``, in a fixed order and without atomics (``maxk_edge_colsum``):
+    ``out[c] = sum_j values[order[j]]`` for ``j`` in ``[ptr_t[c], ptr_t[c + 1])``, with ``ptr_t``
+    int32 ``[num_cols + 1]`` and ``order`` int32 ``[num_edges]`` the transposed structure of the
+    graph (``CSRGraph.transposed_structure()[0]`` and ``CSRGraph.transposed_order()``)."""
+    _check_tensor(ptr_t, "ptr_t", torch.int32)
+    _need(ptr_t.dim() == 1 and ptr_t.numel() >= 1, "ptr_t must have num_cols+1 entries")
+    dev = ptr_t.device
+    _vector(order, "order", torch.int32, None, "num_edges", dev)
+    _vector(values, "values", torch.float32, order.numel(), "num_edges", dev)
+    c = ptr_t.numel() - 1
+    out = _out_vector(out, "out", c, "num_cols", dev)
+    with _device(dev):
+        check(lib.maxk_edge_colsum(_p(ptr_t), _p(order), _p(values), _p(out), c, order.numel(),
+                                   _stream()), "edge_colsum")
+    return out
+
+
 def plan_col_order(plan: GraphPlan) -> torch.Tensor:
     """The plan's column order: int32 [num_cols], position -> column of the backward's column
     blocks (the identity for plans without one)."""
