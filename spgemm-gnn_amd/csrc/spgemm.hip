@@ -1611,8 +1611,9 @@ static int sspmm_backward_impl(const maxk_plan* plan, const int32_t* ptr, const 
 #define ROWS_LAUNCH(RR)                                                                     \
         hipLaunchKernelGGL((sspmm_bwd_rows_kernel<4, RR>), rgrid, dim3(256), 0, s, ptr,    \
                            plan->bwd_erec, grad_out, sp_index, is, tbuf_ws, rb, re, eb, D, k)
-        if (R >= 8) ROWS_LAUNCH(8);
-        else if (R == 4) ROWS_LAUNCH(4);
+        // R is 1, 2 or 4 (choose_bwd_algo doubles it up to kBwdRowsPerWave)
+        static_assert(kBwdRowsPerWave == 4, "one ROWS_LAUNCH per value R can take");
+        if (R == 4) ROWS_LAUNCH(4);
         else if (R == 2) ROWS_LAUNCH(2);
         else ROWS_LAUNCH(1);
 #undef ROWS_LAUNCH
