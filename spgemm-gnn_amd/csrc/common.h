@@ -9,10 +9,10 @@
 
 #include "device_buf.h"
 #include "maxk_hip.h"
+#include "variants.h"
 
 namespace maxk {
 
-constexpr int kWave = 64;               // CDNA wavefront width (never 32)
 constexpr int kFwdTileRows = 32;        // default destination rows per forward work-group
 constexpr int kFwdMaxTileRows = 64;
 // forward LDS accumulator row stride D + kFwdRowPad elements: rows start on different banks,
@@ -22,13 +22,8 @@ constexpr int kFwdRowPad = 1;
 // forward edge word: source column in the low kFwdColBits bits, row within the tile above
 constexpr int kFwdColBits = 26;
 constexpr uint32_t kFwdColMask = (1u << kFwdColBits) - 1;
-constexpr int kFwdThreads = 256;        // 4 waves per forward work-group
 constexpr int kBwdThreads = 512;        // 8 waves per backward work-group (12 at k >= 32)
 constexpr int kMaxDim = 256;            // u8 selectors => D <= 256
-constexpr int kFwdUnroll = 8;           // independent sub-steps in flight per wave
-constexpr int kFwdFlagChunk3 = 1;       // forward kernel flags (template FL): lane-chunk records
-constexpr int kFwdFlagQuad = 2;         // quad-shared edge-word loads
-constexpr int kFwdFlagChunk2 = 4;       // pair-chunk records: 2 values + their selectors per 16 B
 constexpr int kBwdTasksPerCu = 2;
 constexpr int kBwdMinTaskEdges = 100000;  // a chunk's flush (C*k stores) vs its edges
 constexpr int kXcds = 8;
@@ -98,6 +93,22 @@ void set_error(const std::string& msg);
       return (int)_e;                                                           \
     }                                                                           \
   } while (0)
+
+// Runs fn(std::integral_constant<size_t, I>) for the entry I of `table` that equals `v` and
+// returns its result: the launchers name kernel<table[I]...> there, so a family's instantiations
+// are its table's entries. A variant outside the table is an error, not a fallback.
+template <class Table, class V, class Fn, size_t... I>
+int dispatch_variant(const Table& table, const V& v, Fn&& fn, std::index_sequence<I...>) {
+  int rc = MAXK_ERR_UNSUPPORTED;
+  const bool found =
+      ((table[I] == v ? (rc = fn(std::integral_constant<size_t, I>{}), true) : false) || ...);
+  if (!found) set_error("no compiled kernel " + kernel_name(v));
+  return rc;
+}
+template <class Table, class V, class Fn>
+int dispatch_variant(const Table& table, const V& v, Fn&& fn) {
+  return dispatch_variant(table, v, fn, std::make_index_sequence<std::tuple_size<Table>::value>{});
+}
 
 // Whether [a, a + na) and [b, b + nb) (bytes) share a byte.
 inline bool ranges_overlap(const void* a, int64_t na, const void* b, int64_t nb) {
@@ -287,19 +298,21 @@ struct maxk_plan {
   int32_t bwd_handout = 1;
 };
 
-// Whether the plan's forward kernel has a 4-byte edge-word form: the quad-shared windows of 8
-// sub-steps (launch_spgemm_fwd picks the same kernels).
-inline bool plan_fwd_rowconst_shape(const maxk_plan* p) {
-  const int k = p->dim_k;
-  if (!(k % 4 == 0 || p->fwd_chunk3 || p->fwd_chunk2)) return false;
-  const int Lf = p->fwd_chunk3 ? (k + 2) / 3 : p->fwd_chunk2 ? k / 2 : k / 4;  // lanes per edge
-  return p->fwd_quad && Lf % 4 == 0 && p->fwd_unroll == 8 && p->fwd_fix;
-}
-
 // maxk_plan_info.fwd_layout: what the plan's forward gathers from (maxk_hip.h).
 inline int plan_fwd_layout(const maxk_plan* p) {
   if (p->fwd_chunk2) return 4;
   if (p->fwd_chunk3) return 2;
   if (p->dim_k % 4 != 0) return 3;
   return p->fwd_two_tables ? 0 : 1;
+}
+
+// The plan's forward kernel, with 8-byte or 4-byte edge words.
+inline maxk::FwdVariant plan_fwd_variant(const maxk_plan* p, bool rowconst) {
+  return maxk::select_fwd_variant(plan_fwd_layout(p), p->dim_k, p->fwd_fix != nullptr,
+                                  p->fwd_quad != 0, p->fwd_waves, p->fwd_unroll, rowconst);
+}
+
+// Whether the plan's forward kernel has a 4-byte edge-word form.
+inline bool plan_fwd_rowconst_shape(const maxk_plan* p) {
+  return !(plan_fwd_variant(p, true) == maxk::kFwdNoRowconst);
 }

@@ -668,7 +668,7 @@ static int check_options(const maxk_plan_options& o) {
   MAXK_CHECK_ARG(o.bwd_unroll == 0 || o.bwd_unroll == 8 || o.bwd_unroll == 12 ||
                      o.bwd_unroll == 16,
                  "maxk_plan_create: bwd_unroll must be 0, 8, 12 or 16");
-  // the backward shapes that exist (spgemm.hip BWD_SHAPES): 16 waves x 8 sub-steps, 12 x 8 or
+  // the backward shapes that exist (variants.h kBwdVariants): 16 waves x 8 sub-steps, 12 x 8 or
   // 12, 8 x 8, 12 or 16 (an unroll with no kernel is refused, not replaced)
   MAXK_CHECK_ARG(o.bwd_waves != 16 || o.bwd_unroll == 0 || o.bwd_unroll == 8,
                  "maxk_plan_create: bwd_waves 16 runs bwd_unroll 8 only");
@@ -1653,13 +1653,12 @@ static void resolve_launch_shape(PlanBuild& ctx) {
       p->bwd_waves = 12;
     }
   }
-  // the shape that actually launches: the 16-wave shape runs U = 8, 12 waves U
-  // = 8 or 12, and grad_out > 4 GiB (64-bit gathers) one shape, 8 waves x 8
-  if (p->bwd_waves != 8 && !(p->bwd_waves == 12 && p->bwd_unroll == 12)) p->bwd_unroll = 8;
-  if (p->bwd_big) {
-    p->bwd_waves = 8;
-    p->bwd_unroll = 8;
-  }
+  // the shape that actually launches is the launcher's variant, so info()
+  // reports what runs
+  const BwdVariant v = select_bwd_variant(p->bwd_feats, p->bwd_ks / p->bwd_feats, p->bwd_waves,
+                                          p->bwd_unroll, p->bwd_big != 0);
+  p->bwd_waves = v.nt / kWave;
+  p->bwd_unroll = v.u;
 }
 
 // Uploads and the record build; the column order moves into the plan when the column blocks

@@ -124,25 +124,15 @@ static int sddmm_impl(const int32_t* ptr, const int32_t* idx, const float* grad_
                      !ranges_overlap(grad_val, 4 * E, sp_index, (int64_t)(NC - 1) * is + k),
                  w + "grad_val overlaps an input");
   MAXK_CHECK_ARG(NC > 0, w + "num_cols must be > 0 with edges");
-  int K2 = 1;
-  while (K2 < k) K2 <<= 1;
+  const int K2 = sddmm_slots(k);
   const dim3 grid((unsigned)((E + kSddmmChunk - 1) / kSddmmChunk));
-#define MAXK_SDDMM_CASE(LP)                                                                   \
-  case LP:                                                                                    \
-    hipLaunchKernelGGL(sddmm_edge_grad_kernel<LP>, grid, dim3(kSddmmThreads), 0,              \
-                       (hipStream_t)stream, ptr, idx, grad_out, gs, sp_data, ds, sp_index, is, \
-                       grad_val, N, E, k, K2);                                                \
-    break;
-  switch (K2 >= 4 ? K2 / 4 : 1) {  // lanes per edge
-    MAXK_SDDMM_CASE(1)
-    MAXK_SDDMM_CASE(2)
-    MAXK_SDDMM_CASE(4)
-    MAXK_SDDMM_CASE(8)
-    MAXK_SDDMM_CASE(16)
-    MAXK_SDDMM_CASE(32)
-    MAXK_SDDMM_CASE(64)
-  }
-#undef MAXK_SDDMM_CASE
+  if (int e = dispatch_variant(kSddmmVariants, select_sddmm_variant(k), [&](auto i) -> int {
+        hipLaunchKernelGGL(sddmm_edge_grad_kernel<kSddmmVariants[decltype(i)::value].lanes>, grid,
+                           dim3(kSddmmThreads), 0, (hipStream_t)stream, ptr, idx, grad_out, gs,
+                           sp_data, ds, sp_index, is, grad_val, N, E, k, K2);
+        return MAXK_OK;
+      }))
+    return e;
   MAXK_LAUNCH_CHECK("maxk_sddmm_edge_grad launch");
   return MAXK_OK;
 }

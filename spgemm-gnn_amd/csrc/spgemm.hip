@@ -1235,15 +1235,15 @@ static int launch_cbsr_stats(const float* sp_data, int ds, const uint8_t* sp_ind
     const int cap = st0 ? cus * kStatsBlocksPerCu : 8 * cus;
     const int grid = (int)std::max<int64_t>(
         1, std::min<int64_t>((nrows + rows_per_block - 1) / rows_per_block, cap));
-#define STATS4(PK, ST)                                                                      \
-  hipLaunchKernelGGL((cbsr_stats4_kernel<PK, ST>), dim3(grid), dim3(256), 0, s, sp_data, sp_index, \
-                     nrows, k, st0, st1, rec, rec_bytes, zrows, nz, out, D, ds, is)
-    if (rec && st0 && pairs) STATS4(2, true);
-    else if (rec && pairs) STATS4(2, false);
-    else if (rec && st0) STATS4(1, true);
-    else if (rec) STATS4(1, false);
-    else STATS4(0, true);
-#undef STATS4
+    const Stats4Variant v = select_stats4_variant(rec != nullptr, st0 != nullptr, pairs);
+    if (int rc = dispatch_variant(kStats4Variants, v, [&](auto i) -> int {
+          constexpr Stats4Variant V = kStats4Variants[decltype(i)::value];
+          hipLaunchKernelGGL((cbsr_stats4_kernel<V.pack, V.stats>), dim3(grid), dim3(256), 0, s,
+                             sp_data, sp_index, nrows, k, st0, st1, rec, rec_bytes, zrows, nz, out,
+                             D, ds, is);
+          return MAXK_OK;
+        }))
+      return rc;
   } else {
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((nrows + 255) / 256, 2 * cus));
     hipLaunchKernelGGL(cbsr_stats_kernel, dim3(grid), dim3(256), 0, s, sp_data, sp_index, nrows,
@@ -1282,52 +1282,28 @@ static int launch_spgemm_fwd(const maxk_plan* plan, const float* sp_data, int ds
                              const uint8_t* seltab, float* out, int D, int k, int accum,
                              const int2* fix_tab, const uint32_t* xstat, int xs_n, int xs_stride,
                              int xs_off2, size_t lds, hipStream_t s) {
-  const bool pairs = plan->fwd_chunk2;
   if (plan->n_fwd_tasks == 0) return MAXK_OK;
-  const int Lf = plan->fwd_chunk3 ? (k + 2) / 3 : pairs ? k / 2 : k / 4;  // lanes per edge
-  const int FL = (plan->fwd_chunk3 ? kFwdFlagChunk3 : 0) | (pairs ? kFwdFlagChunk2 : 0) |
-                 (plan->fwd_quad && Lf % 4 == 0 ? kFwdFlagQuad : 0);
-  const int fwaves = plan->fwd_waves;
   // 4-byte edge words (plan->fwd_rowconst): the quad kernels of 8 sub-steps only
   const bool rc = plan->fwd_rowconst != 0;
-  if (rc && !plan_fwd_rowconst_shape(plan)) {
+  const FwdVariant v = plan_fwd_variant(plan, rc);
+  if (v == kFwdNoRowconst) {
     set_error("spgemm_fwd launch: 4-byte edge words on a plan whose kernel has none");
     return MAXK_ERR_UNSUPPORTED;
   }
   const void* cvp = rc ? static_cast<const void*>(plan->fwd_cv4.get())
                        : static_cast<const void*>(plan->fwd_cv.get());
-#define FWD_LAUNCH_NT(V, FF, NT, FU, RC)                                                    \
-  do {                                                                                      \
-    if (lds > 64 * 1024) MAXK_HIP_TRY(allow_lds(spgemm_fwd_kernel<V, FF, NT, FU, RC>, lds)); \
-    hipLaunchKernelGGL((spgemm_fwd_kernel<V, FF, NT, FU, RC>), dim3(plan->n_fwd_tasks),     \
-                       dim3(NT), lds, s, plan->fwd_tasks, plan->fwd_phase_off,              \
-                       plan->fwd_phases, cvp, sp_data, sp_index, recp, rec_bytes, out, D, k, \
-                       plan->fwd_rot_ticks, seltab, is, ds, accum, fix_tab, xstat, xs_n,     \
-                       xs_stride, xs_off2, plan->fwd_handout == 2 ? 1 : 0,                  \
-                       plan->fwd_rowval.get());                                             \
-  } while (0)
-#define FWD_LAUNCH(V, FF, RCOK) /* RCOK: the variant has a 4-byte kernel (checked above) */ \
-  do {                                                                                      \
-    if (rc && fwaves == 8) FWD_LAUNCH_NT(V, FF, 8 * kWave, kFwdUnroll, RCOK);               \
-    else if (rc) FWD_LAUNCH_NT(V, FF, kFwdThreads, kFwdUnroll, RCOK);                       \
-    else if (fwaves == 8 && plan->fwd_unroll == 4) FWD_LAUNCH_NT(V, FF, 8 * kWave, 4, false); \
-    else if (fwaves == 8) FWD_LAUNCH_NT(V, FF, 8 * kWave, kFwdUnroll, false);               \
-    else FWD_LAUNCH_NT(V, FF, kFwdThreads, kFwdUnroll, false);                              \
-  } while (0)
-  if (k % 4 == 0 || plan->fwd_chunk3 || plan->fwd_chunk2) {
-    switch (FL) {
-      case 0: FWD_LAUNCH(4, 0, false); break;
-      case kFwdFlagChunk3: FWD_LAUNCH(4, kFwdFlagChunk3, false); break;
-      case kFwdFlagQuad: FWD_LAUNCH(4, kFwdFlagQuad, true); break;
-      case kFwdFlagChunk2: FWD_LAUNCH(4, kFwdFlagChunk2, false); break;
-      case kFwdFlagChunk2 | kFwdFlagQuad: FWD_LAUNCH(4, kFwdFlagChunk2 | kFwdFlagQuad, true); break;
-      default: FWD_LAUNCH(4, kFwdFlagChunk3 | kFwdFlagQuad, true); break;
-    }
-  } else {
-    FWD_LAUNCH(1, 0, false);
-  }
-#undef FWD_LAUNCH
-#undef FWD_LAUNCH_NT
+  if (int e = dispatch_variant(kFwdVariants, v, [&](auto i) -> int {
+        constexpr FwdVariant V = kFwdVariants[decltype(i)::value];
+        auto* kern = spgemm_fwd_kernel<V.v, V.fl, V.nt, V.fu, V.rc>;
+        if (lds > 64 * 1024) MAXK_HIP_TRY(allow_lds(kern, lds));
+        hipLaunchKernelGGL(kern, dim3(plan->n_fwd_tasks), dim3(V.nt), lds, s, plan->fwd_tasks,
+                           plan->fwd_phase_off, plan->fwd_phases, cvp, sp_data, sp_index, recp,
+                           rec_bytes, out, D, k, plan->fwd_rot_ticks, seltab, is, ds, accum,
+                           fix_tab, xstat, xs_n, xs_stride, xs_off2,
+                           plan->fwd_handout == 2 ? 1 : 0, plan->fwd_rowval.get());
+        return MAXK_OK;
+      }))
+    return e;
   MAXK_LAUNCH_CHECK("spgemm_fwd launch");
   return MAXK_OK;
 }
@@ -1405,12 +1381,16 @@ static int spgemm_forward_impl(const maxk_plan* plan, const int32_t* ptr, const 
   const bool pairs = plan->fwd_chunk2;
   const bool pack4 = !two && !inplace && !plan->fwd_chunk3 && k % 4 == 0 && plan->num_cols > 0;
   if ((plan->fwd_chunk3 || (pairs && k % 4 != 0)) && plan->num_cols > 0) {
-    const int V = plan->fwd_chunk3 ? 3 : 2;
-    const int64_t items = (int64_t)plan->num_cols * ((k + V - 1) / V);
+    const PackVariant v = select_pack_variant(plan->fwd_chunk3 != 0);
+    const int64_t items = (int64_t)plan->num_cols * ((k + v.v - 1) / v.v);
     const int grid = (int)std::min<int64_t>((items + 255) / 256, 65536);
-    hipLaunchKernelGGL(V == 3 ? pack_cbsr3_kernel<3> : pack_cbsr3_kernel<2>, dim3(grid), dim3(256),
-                       0, s, sp_data, sp_index, rec_ws, plan->num_cols, k, plan->fwd_rec_bytes,
-                       ds, is);
+    if (int e = dispatch_variant(kPackVariants, v, [&](auto i) -> int {
+          hipLaunchKernelGGL(pack_cbsr3_kernel<kPackVariants[decltype(i)::value].v>, dim3(grid),
+                             dim3(256), 0, s, sp_data, sp_index, rec_ws, plan->num_cols, k,
+                             plan->fwd_rec_bytes, ds, is);
+          return MAXK_OK;
+        }))
+      return e;
     MAXK_LAUNCH_CHECK("pack_cbsr3 launch");
   }
   const bool zero_in_stats = (pack4 || st) && k % 4 == 0;
@@ -1608,15 +1588,15 @@ static int sspmm_backward_impl(const maxk_plan* plan, const int32_t* ptr, const 
       const int64_t eb = plan->tp_edges[p];
       if (re > rb) {
         const dim3 rgrid((re - rb + 4 * R - 1) / (4 * R));
-#define ROWS_LAUNCH(RR)                                                                     \
-        hipLaunchKernelGGL((sspmm_bwd_rows_kernel<4, RR>), rgrid, dim3(256), 0, s, ptr,    \
-                           plan->bwd_erec, grad_out, sp_index, is, tbuf_ws, rb, re, eb, D, k)
         // R is 1, 2 or 4 (choose_bwd_algo doubles it up to kBwdRowsPerWave)
-        static_assert(kBwdRowsPerWave == 4, "one ROWS_LAUNCH per value R can take");
-        if (R == 4) ROWS_LAUNCH(4);
-        else if (R == 2) ROWS_LAUNCH(2);
-        else ROWS_LAUNCH(1);
-#undef ROWS_LAUNCH
+        static_assert(kBwdRowsPerWave == 4, "kRowsVariants holds every value R can take");
+        if (int e = dispatch_variant(kRowsVariants, select_rows_variant(R), [&](auto i) -> int {
+              constexpr RowsVariant V = kRowsVariants[decltype(i)::value];
+              hipLaunchKernelGGL((sspmm_bwd_rows_kernel<V.u, V.r>), rgrid, dim3(256), 0, s, ptr,
+                                 plan->bwd_erec, grad_out, sp_index, is, tbuf_ws, rb, re, eb, D, k);
+              return MAXK_OK;
+            }))
+          return e;
         MAXK_LAUNCH_CHECK("sspmm_bwd_rows launch");
       }
       const int32_t* lo = P > 1 ? plan->bwd_colptr2 + (size_t)p * NC : plan->bwd_colptr;
@@ -1639,34 +1619,18 @@ static int sspmm_backward_impl(const maxk_plan* plan, const int32_t* ptr, const 
   const uint32_t g_bytes = plan->bwd_big ? 0u : (uint32_t)((uint64_t)N * D * 4u);
   const size_t lds = bwd_lds_bytes(plan->bwd_block_cols, ns);
   const dim3 grid(plan->n_bwd_tasks);
-  const bool Q = L % 4 == 0;  // quad-aligned lane groups: batched record loads
-  const int U = plan->bwd_unroll, W = plan->bwd_waves;
-#define BWD_LAUNCH(UU, NT, FF, QQ, BB)                                                      \
-  do {                                                                                      \
-    if (lds > 64 * 1024) MAXK_HIP_TRY(allow_lds(sspmm_bwd4_kernel<UU, NT, FF, QQ, BB>, lds)); \
-    hipLaunchKernelGGL((sspmm_bwd4_kernel<UU, NT, FF, QQ, BB>), grid, dim3(NT), lds, s,     \
-                       plan->bwd_tasks, plan->bwd_rec, grad_out, g_bytes, D, sp_index, is,  \
-                       grad_sp, k, ns, slab, plan->bwd_corder, plan->bwd_handout == 2 ? 1 : 0); \
-  } while (0)
-#define BWD_SHAPES(FF, QQ)                                                                  \
-  do {                                                                                      \
-    if (plan->bwd_big) BWD_LAUNCH(8, 512, FF, QQ, true);                                    \
-    else if (W == 16) BWD_LAUNCH(8, 1024, FF, QQ, false);                                   \
-    else if (W == 12 && U == 12) BWD_LAUNCH(12, 768, FF, QQ, false);                       \
-    else if (W == 12) BWD_LAUNCH(8, 768, FF, QQ, false);                                    \
-    else if (U == 16) BWD_LAUNCH(16, 512, FF, QQ, false);                                   \
-    else if (U == 12) BWD_LAUNCH(12, 512, FF, QQ, false);                                   \
-    else BWD_LAUNCH(8, 512, FF, QQ, false);                                                 \
-  } while (0)
-  if (F == 4) {
-    if (Q) BWD_SHAPES(4, true);
-    else BWD_SHAPES(4, false);
-  } else {
-    if (Q) BWD_SHAPES(2, true);
-    else BWD_SHAPES(2, false);
-  }
-#undef BWD_SHAPES
-#undef BWD_LAUNCH
+  const BwdVariant v =
+      select_bwd_variant(F, L, plan->bwd_waves, plan->bwd_unroll, plan->bwd_big != 0);
+  if (int e = dispatch_variant(kBwdVariants, v, [&](auto i) -> int {
+        constexpr BwdVariant V = kBwdVariants[decltype(i)::value];
+        auto* kern = sspmm_bwd4_kernel<V.u, V.nt, V.f, V.q, V.big>;
+        if (lds > 64 * 1024) MAXK_HIP_TRY(allow_lds(kern, lds));
+        hipLaunchKernelGGL(kern, grid, dim3(V.nt), lds, s, plan->bwd_tasks, plan->bwd_rec,
+                           grad_out, g_bytes, D, sp_index, is, grad_sp, k, ns, slab,
+                           plan->bwd_corder, plan->bwd_handout == 2 ? 1 : 0);
+        return MAXK_OK;
+      }))
+    return e;
   MAXK_LAUNCH_CHECK("sspmm_bwd launch");
   if (slab) {
     const int slices = (plan->bwd_block_cols * k + kCombineSlice - 1) / kCombineSlice;
@@ -1714,19 +1678,15 @@ extern "C" int maxk_dense_spmm_csr(const int32_t* ptr, const int32_t* idx, const
   MAXK_CHECK_ARG(D % 4 == 0, "maxk_dense_spmm_csr: dim must be a multiple of 4");
   if (N == 0) return MAXK_OK;
   MAXK_CHECK_ARG(ptr && X && Y, "maxk_dense_spmm_csr: null pointer");
-  const int C4 = D / 4;
   const dim3 grid((N + 3) / 4), block(256);
   hipStream_t s = (hipStream_t)stream;
-  if (C4 > 32)
-    hipLaunchKernelGGL((dense_spmm_kernel<64, 4>), grid, block, 0, s, ptr, idx, val, X, Y, N, D);
-  else if (C4 > 16)
-    hipLaunchKernelGGL((dense_spmm_kernel<32, 4>), grid, block, 0, s, ptr, idx, val, X, Y, N, D);
-  else if (C4 > 8)
-    hipLaunchKernelGGL((dense_spmm_kernel<16, 4>), grid, block, 0, s, ptr, idx, val, X, Y, N, D);
-  else if (C4 > 4)
-    hipLaunchKernelGGL((dense_spmm_kernel<8, 4>), grid, block, 0, s, ptr, idx, val, X, Y, N, D);
-  else
-    hipLaunchKernelGGL((dense_spmm_kernel<4, 4>), grid, block, 0, s, ptr, idx, val, X, Y, N, D);
+  if (int e = dispatch_variant(kDenseSpmmVariants, select_dense_spmm_variant(D), [&](auto i) -> int {
+        constexpr DenseSpmmVariant V = kDenseSpmmVariants[decltype(i)::value];
+        hipLaunchKernelGGL((dense_spmm_kernel<V.l, V.u>), grid, block, 0, s, ptr, idx, val, X, Y,
+                           N, D);
+        return MAXK_OK;
+      }))
+    return e;
   MAXK_LAUNCH_CHECK("dense_spmm launch");
   return MAXK_OK;
 }

@@ -195,13 +195,13 @@ def maxk_forward(input: torch.Tensor, k: int, mode: str = "exact",
         sbytes = int(lib.maxk_topk_stats_scratch_bytes(n))
         scratch = torch.empty(sbytes, dtype=torch.uint8, device=input.device)
     drop = _dropout_arg(dropout)
+    buf, layout, rb = None, 0, 0
+    if records is not None:
+        buf, layout = records
+        rb = _records(buf, layout, n, k, "records")
+        _need(buf.device == input.device, "records must be on the input's device")
     with _device(input.device):
         if dense is not None:
-            buf, layout, rb = None, 0, 0
-            if records is not None:
-                buf, layout = records
-                rb = _records(buf, layout, n, k, "records")
-                _need(buf.device == input.device, "records must be on the input's device")
             p, seed, row_offset = drop if drop is not None else (0.0, 0, 0)
             check(lib.maxk_topk_cbsr_dense(_p(input), _p(dense), dstride, _p(buf), rb, int(layout),
                                            _p(sp_data if return_values else None), ds,
@@ -211,11 +211,6 @@ def maxk_forward(input: torch.Tensor, k: int, mode: str = "exact",
             if not return_values:
                 sp_data = None
         elif drop is not None:
-            buf, layout, rb = None, 0, 0
-            if records is not None:
-                buf, layout = records
-                rb = _records(buf, layout, n, k, "records")
-                _need(buf.device == input.device, "records must be on the input's device")
             check(lib.maxk_topk_cbsr_dropout(_p(input), _p(buf), rb, int(layout),
                                              _p(sp_data if return_values else None), ds,
                                              _p(sp_index), is_, _p(count), _p(stats), _p(scratch),
@@ -224,9 +219,6 @@ def maxk_forward(input: torch.Tensor, k: int, mode: str = "exact",
             if not return_values:
                 sp_data = None
         elif records is not None:
-            buf, layout = records
-            rb = _records(buf, layout, n, k, "records")
-            _need(buf.device == input.device, "records must be on the input's device")
             check(lib.maxk_topk_cbsr_records(_p(input), _p(buf), rb, int(layout),
                                              _p(sp_data if return_values else None), ds,
                                              _p(sp_index), is_, _p(count), _p(stats), _p(scratch),

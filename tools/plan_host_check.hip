@@ -66,8 +66,15 @@ static void check_shapes_and_chunks(int N, int NC, int64_t E, int D, int k, int 
   choose_bwd_shape(ctx);
   const maxk_plan* p = ctx.plan.get();
   CHECK(p->fwd_tile_rows >= 1 && p->fwd_tile_rows <= kFwdMaxTileRows);
+  // the shapes have a kernel: the variants they select are in the compiled tables
   CHECK(p->fwd_waves == 4 || p->fwd_waves == 8);
+  CHECK(has_variant(kFwdVariants, plan_fwd_variant(p, false)));
+  CHECK(!plan_fwd_rowconst_shape(p) || has_variant(kFwdVariants, plan_fwd_variant(p, true)));
   CHECK(p->bwd_feats == 2 || p->bwd_feats == 4);
+  for (int big = 0; big < 2; ++big)
+    CHECK(has_variant(kBwdVariants,
+                      select_bwd_variant(p->bwd_feats, p->bwd_kp / p->bwd_slot_groups / p->bwd_feats,
+                                         p->bwd_waves, p->bwd_unroll, big != 0)));
   CHECK(p->bwd_kp >= k && p->bwd_kp % (p->bwd_feats * p->bwd_slot_groups) == 0);
   CHECK(ctx.C >= 1 && ctx.C <= std::max(NC, 1) && ctx.S >= 1);
   if (nblocks > 0 && E > 0) {
