@@ -71,46 +71,16 @@ __device__ __forceinline__ float gat_row_score(const float* __restrict__ er, int
   return er[row < num_rows ? row : num_rows - 1];
 }
 
+// The kernels' bodies are the three .inc files beside this one, included by the single-head
+// kernel and by its head-batched twin: the single-head kernels compile from exactly the statements
+// they always had (an inlined device function gave other register allocation and branch polarity).
 // ---------------------------------------------------------------------------------- forward
 // The tile logic of edge_softmax_fwd_kernel with GatScore for EsArray.
 __global__ __launch_bounds__(kEsThreads) void gat_attention_fwd_kernel(
     const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx,
     const float* __restrict__ el, const float* __restrict__ er, float slope,
     float* __restrict__ out, int32_t num_rows, int32_t num_cols, int64_t E) {
-  __shared__ float red[2 * kEsWaves];
-  const int tid = threadIdx.x;
-  const int lane = tid & (kWave - 1), wave = tid / kWave;
-  const int64_t row0 = (int64_t)blockIdx.x * kEsTileRows;
-  const int32_t col_hi = num_cols - 1;
-
-  int64_t b;
-  int32_t n;
-  const int64_t row = row0 + wave * kEsWaveRows + lane / kEsGroup;
-  es_segment(ptr, row, num_rows, E, b, n);
-  const int32_t ns = n <= kEsShortMax ? n : 0;
-  if (__ballot(ns > 0) != 0) {
-    // a group with no short row scores edge 0 (E > 0) and writes nothing
-    const int64_t bs = ns > 0 ? b : 0;
-    const GatScore src{idx + bs, el, gat_row_score(er, row, num_rows), slope, col_hi};
-    es_fwd_regs<kEsGroup, kEsShortSlots>(src, out + bs, ns, lane % kEsGroup);
-  }
-#pragma unroll
-  for (int g = 0; g < kEsWaveRows; ++g) {
-    const int32_t ng = __shfl(n, g * kEsGroup, kWave);
-    if (ng <= kEsShortMax || ng > kEsMediumMax) continue;  // wave-uniform
-    const int64_t bg = __shfl(b, g * kEsGroup, kWave);
-    const GatScore src{idx + bg, el, er[row0 + wave * kEsWaveRows + g], slope, col_hi};
-    es_fwd_medium(src, out + bg, ng, lane);
-  }
-
-  for (int r = 0; r < kEsTileRows; ++r) {
-    int64_t bh;
-    int32_t nh;
-    es_segment(ptr, row0 + r, num_rows, E, bh, nh);
-    if (nh <= kEsMediumMax) continue;
-    const GatScore src{idx + bh, el, er[row0 + r], slope, col_hi};
-    es_fwd_hub<true>(src, out + bh, nh, tid, lane, wave, red);
-  }
+#include "gat_attention_fwd.inc"
 }
 
 // --------------------------------------------------------------------------------- backward
@@ -121,95 +91,61 @@ __global__ __launch_bounds__(kEsThreads) void gat_attention_bwd_kernel(
     const float* __restrict__ el, const float* __restrict__ er, float slope,
     const float* __restrict__ y, const float* __restrict__ gy, float* __restrict__ out,
     float* __restrict__ grad_er, int32_t num_rows, int32_t num_cols, int64_t E) {
-  __shared__ float red[kEsWaves];
-  __shared__ float red2[kEsWaves];
-  const int tid = threadIdx.x;
-  const int lane = tid & (kWave - 1), wave = tid / kWave;
-  const int64_t row0 = (int64_t)blockIdx.x * kEsTileRows;
-  const int32_t col_hi = num_cols - 1;
-
-  int64_t b;
-  int32_t n;
-  const int64_t row = row0 + wave * kEsWaveRows + lane / kEsGroup;
-  es_segment(ptr, row, num_rows, E, b, n);
-  const int32_t ns = n <= kEsShortMax ? n : 0;
-  float s = 0.f;
-  if (__ballot(ns > 0) != 0) {
-    const int64_t bs = ns > 0 ? b : 0;
-    const GatScore post{idx + bs, el, gat_row_score(er, row, num_rows), slope, col_hi};
-    s = es_sum<kEsGroup>(es_bwd_regs<kEsGroup, kEsShortSlots>(y + bs, gy + bs, out + bs, ns,
-                                                              lane % kEsGroup, post));
-  }
-  if (row < num_rows && n <= kEsShortMax && lane % kEsGroup == 0) grad_er[row] = s;
-#pragma unroll
-  for (int g = 0; g < kEsWaveRows; ++g) {
-    const int32_t ng = __shfl(n, g * kEsGroup, kWave);
-    if (ng <= kEsShortMax || ng > kEsMediumMax) continue;  // wave-uniform
-    const int64_t bg = __shfl(b, g * kEsGroup, kWave);
-    const int64_t rg = row0 + wave * kEsWaveRows + g;
-    const GatScore post{idx + bg, el, er[rg], slope, col_hi};
-    const float sg = es_sum<kWave>(es_bwd_medium(y + bg, gy + bg, out + bg, ng, lane, post));
-    if (lane == 0) grad_er[rg] = sg;
-  }
-
-  for (int r = 0; r < kEsTileRows; ++r) {
-    int64_t bh;
-    int32_t nh;
-    es_segment(ptr, row0 + r, num_rows, E, bh, nh);
-    if (nh <= kEsMediumMax) continue;
-    const GatScore post{idx + bh, el, er[row0 + r], slope, col_hi};
-    const float acc = es_bwd_hub(y + bh, gy + bh, out + bh, nh, tid, lane, wave, red, post);
-    const float sh = es_hub_combine(acc, lane, wave, red2);  // its barrier frees red
-    if (tid == 0) grad_er[row0 + r] = sh;
-    // red2 is written again only behind the next hub's first barrier
-  }
+#include "gat_attention_bwd.inc"
 }
 
 // ------------------------------------------------------------------------------- column sum
 __global__ __launch_bounds__(kEsThreads) void edge_colsum_kernel(
     const int32_t* __restrict__ ptr_t, const int32_t* __restrict__ order,
     const float* __restrict__ values, float* __restrict__ out, int32_t num_cols, int64_t E) {
-  __shared__ float red[kEsWaves];
-  const int tid = threadIdx.x;
-  const int lane = tid & (kWave - 1), wave = tid / kWave;
-  const int64_t col0 = (int64_t)blockIdx.x * kEsTileRows;
-  const int32_t edge_hi = (int32_t)(E - 1);
-
-  int64_t b;
-  int32_t n;
-  const int64_t col = col0 + wave * kEsWaveRows + lane / kEsGroup;
-  es_segment(ptr_t, col, num_cols, E, b, n);
-  const int32_t ns = n <= kEsShortMax ? n : 0;
-  float s = 0.f;
-  if (__ballot(ns > 0) != 0) {
-    const int64_t bs = ns > 0 ? b : 0;
-    s = es_sum_regs<kEsGroup, kEsShortSlots>(GatPermuted{order + bs, values, edge_hi}, ns,
-                                             lane % kEsGroup);
-  }
-  if (col < num_cols && n <= kEsShortMax && lane % kEsGroup == 0) out[col] = s;
-#pragma unroll
-  for (int g = 0; g < kEsWaveRows; ++g) {
-    const int32_t ng = __shfl(n, g * kEsGroup, kWave);
-    if (ng <= kEsShortMax || ng > kEsMediumMax) continue;  // wave-uniform
-    const int64_t bg = __shfl(b, g * kEsGroup, kWave);
-    const float sg = es_sum_medium(GatPermuted{order + bg, values, edge_hi}, ng, lane);
-    if (lane == 0) out[col0 + wave * kEsWaveRows + g] = sg;
-  }
-
-  for (int r = 0; r < kEsTileRows; ++r) {
-    int64_t bh;
-    int32_t nh;
-    es_segment(ptr_t, col0 + r, num_cols, E, bh, nh);
-    if (nh <= kEsMediumMax) continue;
-    const GatPermuted src{order + bh, values, edge_hi};
-    float a = 0.f;
-#pragma unroll kEsHubUnroll
-    for (int32_t j = tid; j < nh; j += kEsThreads) a = a + src(j);
-    const float sh = es_hub_combine(a, lane, wave, red);
-    if (tid == 0) out[col0 + r] = sh;
-    __syncthreads();  // red is free for the tile's next hub
-  }
+#include "edge_colsum.inc"
 }
+
+}  // namespace maxk
+
+// The head-batched kernels (include/maxk_hip.h, "GAT attention, heads"): the same bodies on head
+// blockIdx.y of the head-major arrays, so head h of a batched call carries the bits of the
+// single-head call on row h by construction. Kernels of their own, outside namespace maxk
+// (DESIGN section 4.12).
+namespace maxk_mh {
+
+using namespace maxk;
+
+__global__ __launch_bounds__(kEsThreads) void gat_attention_fwd_heads_kernel(
+    const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx,
+    const float* __restrict__ el, const float* __restrict__ er, float slope,
+    float* __restrict__ out, int32_t num_rows, int32_t num_cols, int64_t E) {
+  el += (int64_t)blockIdx.y * num_cols;
+  er += (int64_t)blockIdx.y * num_rows;
+  out += (int64_t)blockIdx.y * E;
+#include "gat_attention_fwd.inc"
+}
+
+__global__ __launch_bounds__(kEsThreads) void gat_attention_bwd_heads_kernel(
+    const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx,
+    const float* __restrict__ el, const float* __restrict__ er, float slope,
+    const float* __restrict__ y, const float* __restrict__ gy, float* __restrict__ out,
+    float* __restrict__ grad_er, int32_t num_rows, int32_t num_cols, int64_t E) {
+  el += (int64_t)blockIdx.y * num_cols;
+  er += (int64_t)blockIdx.y * num_rows;
+  y += (int64_t)blockIdx.y * E;
+  gy += (int64_t)blockIdx.y * E;
+  out += (int64_t)blockIdx.y * E;
+  grad_er += (int64_t)blockIdx.y * num_rows;
+#include "gat_attention_bwd.inc"
+}
+
+__global__ __launch_bounds__(kEsThreads) void edge_colsum_heads_kernel(
+    const int32_t* __restrict__ ptr_t, const int32_t* __restrict__ order,
+    const float* __restrict__ values, float* __restrict__ out, int32_t num_cols, int64_t E) {
+  values += (int64_t)blockIdx.y * E;
+  out += (int64_t)blockIdx.y * num_cols;
+#include "edge_colsum.inc"
+}
+
+}  // namespace maxk_mh
+
+namespace maxk {
 
 // ------------------------------------------------------------------------------ entry points
 struct GatRange {
@@ -241,30 +177,138 @@ static int gat_check_sizes(const std::string& w, int32_t num_rows, int32_t num_c
   return MAXK_OK;
 }
 
-}  // namespace maxk
+// The head-major arrays of H heads: H within the grid's second dimension, and every array's
+// byte size (4 H times its per-head length) within int64.
+static int gat_check_heads(const std::string& w, int32_t H, int32_t num_rows, int32_t num_cols,
+                           int64_t E) {
+  MAXK_CHECK_ARG(H >= 1, w + "num_heads must be >= 1");
+  int64_t longest = E > num_rows ? E : num_rows;
+  longest = longest > num_cols ? longest : num_cols;
+  MAXK_CHECK_ARG(H <= 65535 && (int64_t)H <= (INT64_MAX / 4) / (longest > 0 ? longest : 1),
+                 w + "num_heads * num_edges is beyond what the offsets can address");
+  return MAXK_OK;
+}
 
-extern "C" int maxk_gat_attention_forward(const int32_t* ptr, const int32_t* idx, const float* el,
-                                          const float* er, float negative_slope, float* alpha,
-                                          int32_t num_rows, int32_t num_cols, int64_t num_edges,
-                                          void* stream) {
-  using namespace maxk;
-  const std::string w = "maxk_gat_attention_forward: ";
+static dim3 gat_grid(int32_t n, int32_t H) {
+  dim3 g = es_grid(n);
+  g.y = (unsigned)H;
+  return g;
+}
+
+static int gat_forward_impl(const std::string& w, const int32_t* ptr, const int32_t* idx,
+                            const float* el, const float* er, float negative_slope, float* alpha,
+                            bool heads, int32_t H, int32_t num_rows, int32_t num_cols,
+                            int64_t num_edges, void* stream) {
   int rc = gat_check_sizes(w, num_rows, num_cols, num_edges);
+  if (rc != MAXK_OK) return rc;
+  rc = gat_check_heads(w, H, num_rows, num_cols, num_edges);
   if (rc != MAXK_OK) return rc;
   MAXK_CHECK_ARG(std::isfinite(negative_slope), w + "negative_slope must be finite");
   if (num_edges == 0 || num_rows == 0) return MAXK_OK;
   MAXK_CHECK_ARG(num_cols > 0, w + "sizes out of range: edges without columns");
   const int64_t E = num_edges;
   const GatRange ins[4] = {{ptr, 4 * ((int64_t)num_rows + 1)}, {idx, 4 * E},
-                           {el, 4 * (int64_t)num_cols}, {er, 4 * (int64_t)num_rows}};
-  const GatRange outs[1] = {{alpha, 4 * E}};
+                           {el, 4 * H * (int64_t)num_cols}, {er, 4 * H * (int64_t)num_rows}};
+  const GatRange outs[1] = {{alpha, 4 * H * E}};
   rc = gat_check_ranges(w, ins, 4, outs, 1);
   if (rc != MAXK_OK) return rc;
-  hipLaunchKernelGGL(gat_attention_fwd_kernel, es_grid(num_rows), dim3(kEsThreads), 0,
-                     (hipStream_t)stream, ptr, idx, el, er, negative_slope, alpha, num_rows,
-                     num_cols, E);
-  MAXK_LAUNCH_CHECK("maxk_gat_attention_forward launch");
+  if (heads)
+    hipLaunchKernelGGL(maxk_mh::gat_attention_fwd_heads_kernel, gat_grid(num_rows, H),
+                       dim3(kEsThreads), 0, (hipStream_t)stream, ptr, idx, el, er, negative_slope,
+                       alpha, num_rows, num_cols, E);
+  else
+    hipLaunchKernelGGL(gat_attention_fwd_kernel, es_grid(num_rows), dim3(kEsThreads), 0,
+                       (hipStream_t)stream, ptr, idx, el, er, negative_slope, alpha, num_rows,
+                       num_cols, E);
+  MAXK_LAUNCH_CHECK((w + "launch").c_str());
   return MAXK_OK;
+}
+
+static int gat_backward_impl(const std::string& w, const int32_t* ptr, const int32_t* idx,
+                             const float* el, const float* er, float negative_slope,
+                             const float* alpha, const float* grad_alpha, float* grad_edge,
+                             float* grad_er, bool heads, int32_t H, int32_t num_rows,
+                             int32_t num_cols, int64_t num_edges, void* stream) {
+  int rc = gat_check_sizes(w, num_rows, num_cols, num_edges);
+  if (rc != MAXK_OK) return rc;
+  rc = gat_check_heads(w, H, num_rows, num_cols, num_edges);
+  if (rc != MAXK_OK) return rc;
+  MAXK_CHECK_ARG(std::isfinite(negative_slope), w + "negative_slope must be finite");
+  if (num_rows == 0) return MAXK_OK;
+  const int64_t E = num_edges;
+  if (E == 0) {  // no edge, so every row is empty: grad_er is zeros and grad_edge has no element
+    MAXK_CHECK_ARG(grad_er, w + "null pointer");
+    MAXK_HIP_TRY(hipMemsetAsync(grad_er, 0, 4 * (size_t)H * (size_t)num_rows,
+                                (hipStream_t)stream));
+    return MAXK_OK;
+  }
+  MAXK_CHECK_ARG(num_cols > 0, w + "sizes out of range: edges without columns");
+  const GatRange ins[6] = {{ptr, 4 * ((int64_t)num_rows + 1)}, {idx, 4 * E},
+                           {el, 4 * H * (int64_t)num_cols}, {er, 4 * H * (int64_t)num_rows},
+                           {alpha, 4 * H * E}, {grad_alpha, 4 * H * E}};
+  const GatRange outs[2] = {{grad_edge, 4 * H * E}, {grad_er, 4 * H * (int64_t)num_rows}};
+  rc = gat_check_ranges(w, ins, 6, outs, 2);
+  if (rc != MAXK_OK) return rc;
+  if (heads)
+    hipLaunchKernelGGL(maxk_mh::gat_attention_bwd_heads_kernel, gat_grid(num_rows, H),
+                       dim3(kEsThreads), 0, (hipStream_t)stream, ptr, idx, el, er, negative_slope,
+                       alpha, grad_alpha, grad_edge, grad_er, num_rows, num_cols, E);
+  else
+    hipLaunchKernelGGL(gat_attention_bwd_kernel, es_grid(num_rows), dim3(kEsThreads), 0,
+                       (hipStream_t)stream, ptr, idx, el, er, negative_slope, alpha, grad_alpha,
+                       grad_edge, grad_er, num_rows, num_cols, E);
+  MAXK_LAUNCH_CHECK((w + "launch").c_str());
+  return MAXK_OK;
+}
+
+static int gat_colsum_impl(const std::string& w, const int32_t* ptr_t, const int32_t* order,
+                           const float* values, float* out, bool heads, int32_t H,
+                           int32_t num_cols, int64_t num_edges, void* stream) {
+  int rc = gat_check_sizes(w, 0, num_cols, num_edges);
+  if (rc != MAXK_OK) return rc;
+  rc = gat_check_heads(w, H, 0, num_cols, num_edges);
+  if (rc != MAXK_OK) return rc;
+  if (num_cols == 0) return MAXK_OK;
+  const int64_t E = num_edges;
+  if (E == 0) {
+    MAXK_CHECK_ARG(out, w + "null pointer");
+    MAXK_HIP_TRY(hipMemsetAsync(out, 0, 4 * (size_t)H * (size_t)num_cols, (hipStream_t)stream));
+    return MAXK_OK;
+  }
+  const GatRange ins[3] = {{ptr_t, 4 * ((int64_t)num_cols + 1)}, {order, 4 * E},
+                           {values, 4 * H * E}};
+  const GatRange outs[1] = {{out, 4 * H * (int64_t)num_cols}};
+  rc = gat_check_ranges(w, ins, 3, outs, 1);
+  if (rc != MAXK_OK) return rc;
+  if (heads)
+    hipLaunchKernelGGL(maxk_mh::edge_colsum_heads_kernel, gat_grid(num_cols, H), dim3(kEsThreads),
+                       0, (hipStream_t)stream, ptr_t, order, values, out, num_cols, E);
+  else
+    hipLaunchKernelGGL(edge_colsum_kernel, es_grid(num_cols), dim3(kEsThreads), 0,
+                       (hipStream_t)stream, ptr_t, order, values, out, num_cols, E);
+  MAXK_LAUNCH_CHECK((w + "launch").c_str());
+  return MAXK_OK;
+}
+
+}  // namespace maxk
+
+extern "C" int maxk_gat_attention_forward(const int32_t* ptr, const int32_t* idx, const float* el,
+                                          const float* er, float negative_slope, float* alpha,
+                                          int32_t num_rows, int32_t num_cols, int64_t num_edges,
+                                          void* stream) {
+  return maxk::gat_forward_impl("maxk_gat_attention_forward: ", ptr, idx, el, er, negative_slope,
+                                alpha, false, 1, num_rows, num_cols, num_edges, stream);
+}
+
+extern "C" int maxk_gat_attention_forward_heads(const int32_t* ptr, const int32_t* idx,
+                                                const float* el, const float* er,
+                                                float negative_slope, float* alpha,
+                                                int32_t num_heads, int32_t num_rows,
+                                                int32_t num_cols, int64_t num_edges,
+                                                void* stream) {
+  return maxk::gat_forward_impl("maxk_gat_attention_forward_heads: ", ptr, idx, el, er,
+                                negative_slope, alpha, true, num_heads, num_rows, num_cols,
+                                num_edges, stream);
 }
 
 extern "C" int maxk_gat_attention_backward(const int32_t* ptr, const int32_t* idx, const float* el,
@@ -272,51 +316,32 @@ extern "C" int maxk_gat_attention_backward(const int32_t* ptr, const int32_t* id
                                            const float* alpha, const float* grad_alpha,
                                            float* grad_edge, float* grad_er, int32_t num_rows,
                                            int32_t num_cols, int64_t num_edges, void* stream) {
-  using namespace maxk;
-  const std::string w = "maxk_gat_attention_backward: ";
-  int rc = gat_check_sizes(w, num_rows, num_cols, num_edges);
-  if (rc != MAXK_OK) return rc;
-  MAXK_CHECK_ARG(std::isfinite(negative_slope), w + "negative_slope must be finite");
-  if (num_rows == 0) return MAXK_OK;
-  const int64_t E = num_edges;
-  if (E == 0) {  // no edge, so every row is empty: grad_er is zeros and grad_edge has no element
-    MAXK_CHECK_ARG(grad_er, w + "null pointer");
-    MAXK_HIP_TRY(hipMemsetAsync(grad_er, 0, 4 * (size_t)num_rows, (hipStream_t)stream));
-    return MAXK_OK;
-  }
-  MAXK_CHECK_ARG(num_cols > 0, w + "sizes out of range: edges without columns");
-  const GatRange ins[6] = {{ptr, 4 * ((int64_t)num_rows + 1)}, {idx, 4 * E},
-                           {el, 4 * (int64_t)num_cols}, {er, 4 * (int64_t)num_rows},
-                           {alpha, 4 * E}, {grad_alpha, 4 * E}};
-  const GatRange outs[2] = {{grad_edge, 4 * E}, {grad_er, 4 * (int64_t)num_rows}};
-  rc = gat_check_ranges(w, ins, 6, outs, 2);
-  if (rc != MAXK_OK) return rc;
-  hipLaunchKernelGGL(gat_attention_bwd_kernel, es_grid(num_rows), dim3(kEsThreads), 0,
-                     (hipStream_t)stream, ptr, idx, el, er, negative_slope, alpha, grad_alpha,
-                     grad_edge, grad_er, num_rows, num_cols, E);
-  MAXK_LAUNCH_CHECK("maxk_gat_attention_backward launch");
-  return MAXK_OK;
+  return maxk::gat_backward_impl("maxk_gat_attention_backward: ", ptr, idx, el, er,
+                                 negative_slope, alpha, grad_alpha, grad_edge, grad_er, false, 1,
+                                 num_rows, num_cols, num_edges, stream);
+}
+
+extern "C" int maxk_gat_attention_backward_heads(const int32_t* ptr, const int32_t* idx,
+                                                 const float* el, const float* er,
+                                                 float negative_slope, const float* alpha,
+                                                 const float* grad_alpha, float* grad_edge,
+                                                 float* grad_er, int32_t num_heads,
+                                                 int32_t num_rows, int32_t num_cols,
+                                                 int64_t num_edges, void* stream) {
+  return maxk::gat_backward_impl("maxk_gat_attention_backward_heads: ", ptr, idx, el, er,
+                                 negative_slope, alpha, grad_alpha, grad_edge, grad_er, true,
+                                 num_heads, num_rows, num_cols, num_edges, stream);
 }
 
 extern "C" int maxk_edge_colsum(const int32_t* ptr_t, const int32_t* order, const float* values,
                                 float* out, int32_t num_cols, int64_t num_edges, void* stream) {
-  using namespace maxk;
-  const std::string w = "maxk_edge_colsum: ";
-  int rc = gat_check_sizes(w, 0, num_cols, num_edges);
-  if (rc != MAXK_OK) return rc;
-  if (num_cols == 0) return MAXK_OK;
-  const int64_t E = num_edges;
-  if (E == 0) {
-    MAXK_CHECK_ARG(out, w + "null pointer");
-    MAXK_HIP_TRY(hipMemsetAsync(out, 0, 4 * (size_t)num_cols, (hipStream_t)stream));
-    return MAXK_OK;
-  }
-  const GatRange ins[3] = {{ptr_t, 4 * ((int64_t)num_cols + 1)}, {order, 4 * E}, {values, 4 * E}};
-  const GatRange outs[1] = {{out, 4 * (int64_t)num_cols}};
-  rc = gat_check_ranges(w, ins, 3, outs, 1);
-  if (rc != MAXK_OK) return rc;
-  hipLaunchKernelGGL(edge_colsum_kernel, es_grid(num_cols), dim3(kEsThreads), 0,
-                     (hipStream_t)stream, ptr_t, order, values, out, num_cols, E);
-  MAXK_LAUNCH_CHECK("maxk_edge_colsum launch");
-  return MAXK_OK;
+  return maxk::gat_colsum_impl("maxk_edge_colsum: ", ptr_t, order, values, out, false, 1,
+                               num_cols, num_edges, stream);
+}
+
+extern "C" int maxk_edge_colsum_heads(const int32_t* ptr_t, const int32_t* order,
+                                      const float* values, float* out, int32_t num_heads,
+                                      int32_t num_cols, int64_t num_edges, void* stream) {
+  return maxk::gat_colsum_impl("maxk_edge_colsum_heads: ", ptr_t, order, values, out, true,
+                               num_heads, num_cols, num_edges, stream);
 }

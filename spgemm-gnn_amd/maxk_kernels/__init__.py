@@ -23,6 +23,7 @@ from .ops import (  # noqa: F401
     edge_softmax_backward,
     edge_softmax_row_limits,
     get_plan,
+    heads_row_limits,
     maxk_backward,
     maxk_forward,
     plan_col_order,
@@ -51,6 +52,13 @@ from .autograd import (  # noqa: F401
 
 from . import torch_ops  # noqa: F401,E402  (registers torch.ops.maxk.*)
 from .attention import GATAttentionFunction, gat_attention  # noqa: F401,E402  (and its operators)
+from .heads import (  # noqa: F401,E402  (and its operators)
+    GATAttentionHeadsFunction,
+    HeadsAggregateFunction,
+    gat_attention_heads,
+    heads_aggregate,
+    maxk_heads_aggregate,
+)
 from .layers import (  # noqa: F401,E402
     MaxKGCN,
     MaxKGATConv,
@@ -70,6 +78,8 @@ __all__ = [
     "maxk_self_aggregate", "spgemm_edge_grad", "EdgeWeightedFunction", "DenseEdgeWeightedFunction",
     "edge_softmax", "edge_softmax_backward", "edge_softmax_row_limits", "EdgeSoftmaxFunction",
     "MaxKGATConv", "gat_attention", "GATAttentionFunction",
+    "gat_attention_heads", "GATAttentionHeadsFunction", "heads_aggregate", "maxk_heads_aggregate",
+    "HeadsAggregateFunction", "heads_row_limits",
 ]
 
 ABI_VERSION = lib.maxk_abi_version()

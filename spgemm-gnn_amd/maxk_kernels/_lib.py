@@ -92,6 +92,18 @@ SIGNATURES = {
     "maxk_gat_attention_backward": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_float, _vp, _vp,
                                                    _vp, _vp, _i32, _i32, _i64, _vp]),
     "maxk_edge_colsum": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i64, _vp]),
+    "maxk_gat_attention_forward_heads": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_float, _vp,
+                                                        _i32, _i32, _i32, _i64, _vp]),
+    "maxk_gat_attention_backward_heads": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_float, _vp,
+                                                         _vp, _vp, _vp, _i32, _i32, _i32, _i64,
+                                                         _vp]),
+    "maxk_edge_colsum_heads": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i64, _vp]),
+    "maxk_heads_aggregate_forward": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i32,
+                                                    _i32, _i32, _i64, _i32, _i32, _vp]),
+    "maxk_heads_aggregate_backward": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp,
+                                                     _i64, _vp, _vp, _i32, _i32, _i32, _i64, _i32,
+                                                     _i32, _vp]),
+    "maxk_heads_row_limits": (ctypes.c_int, [_vp, _i32]),
     "maxk_dense_spmm_csr": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "maxk_warp4_build": (ctypes.c_int, [_vp, _i32, _i32, _vp, _i64, ctypes.POINTER(_i64)]),
 }

@@ -77,6 +77,7 @@ import torch.nn.functional as F
 from .autograd import (CSRGraph, dense_aggregate, densify, edge_softmax, maxk, maxk_aggregate,
                        maxk_self_aggregate, spgemm)
 from .attention import gat_attention
+from .heads import gat_attention_heads, heads_aggregate, maxk_heads_aggregate
 
 NONLINEAR = ("maxk", "relu")
 
@@ -274,12 +275,29 @@ class MaxKGATConv(nn.Module):
     score gradients its two backward kernels: the same ``alpha`` and output bit for bit, no
     ``[E]`` intermediates, and gradients to ``attn_l``, ``attn_r`` and ``fc`` summed in a fixed
     order that is another order than ``index_add``'s. The attention needs the CSRGraph's own
-    edge order, so a DGL graph raises the ``TypeError`` of ``edge_weight=``."""
+    edge order, so a DGL graph raises the ``TypeError`` of ``edge_weight=``.
+
+    ``num_heads=H > 1`` is ``dglnn.GATConv(num_heads=H)``: ``fc`` maps to ``H * out_feats <=
+    256``, ``attn_l`` / ``attn_r`` are ``(H, out_feats)``, the bias has ``H * out_feats`` entries
+    and the result is ``[N, H, out_feats]``. MaxK keeps ``maxk`` features of the whole
+    ``H * out_feats`` row; the attention is always the fused head-batched kernel and the
+    aggregation the multi-head one (:mod:`maxk_kernels.heads`), which builds no plan.
+    ``nonlinear="relu"`` is not implemented for ``H > 1``. The default ``num_heads=1`` is the
+    single-head layer above, unchanged."""
 
     def __init__(self, in_feats, out_feats, maxk=32, negative_slope=0.2, attn_drop=0.,
                  feat_drop=0., bias=True, allow_zero_in_degree=False, topk_mode="exact",
-                 nonlinear="maxk", fused_dropout=False, fused_attention=False):
+                 nonlinear="maxk", fused_dropout=False, fused_attention=False, num_heads=1):
         super().__init__()
+        self.num_heads = int(num_heads)
+        if self.num_heads < 1:
+            raise ValueError(f"num_heads must be >= 1, got {num_heads}")
+        if self.num_heads > 1 and nonlinear == "relu":
+            raise NotImplementedError('nonlinear="relu" with num_heads > 1: the dense multi-head '
+                                      "aggregation is not implemented")
+        if self.num_heads > 1 and self.num_heads * out_feats > 256:
+            raise ValueError("num_heads * out_feats = D <= 256 (u8 selectors), got "
+                             f"{self.num_heads * out_feats}")
         self.fused_dropout = bool(fused_dropout)
         self.fused_attention = bool(fused_attention)
         self.in_feats = in_feats
@@ -291,10 +309,10 @@ class MaxKGATConv(nn.Module):
         self.allow_zero_in_degree = allow_zero_in_degree
         self.topk_mode = topk_mode
         self.nonlinear = _check_nonlinear(nonlinear)
-        self.fc = nn.Linear(in_feats, out_feats, bias=False)
-        self.attn_l = nn.Parameter(torch.empty(1, out_feats))
-        self.attn_r = nn.Parameter(torch.empty(1, out_feats))
-        self.bias = nn.Parameter(torch.empty(out_feats)) if bias else None
+        self.fc = nn.Linear(in_feats, self.num_heads * out_feats, bias=False)
+        self.attn_l = nn.Parameter(torch.empty(self.num_heads, out_feats))
+        self.attn_r = nn.Parameter(torch.empty(self.num_heads, out_feats))
+        self.bias = nn.Parameter(torch.empty(self.num_heads * out_feats)) if bias else None
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -310,6 +328,8 @@ class MaxKGATConv(nn.Module):
         if not self.allow_zero_in_degree and bool((csr.in_degrees() == 0).any()):
             raise ValueError("Graph has nodes with zero in-degree")
         h = self.fc(feat)
+        if self.num_heads > 1:
+            return self._forward_heads(csr, h)
         el = (h * self.attn_l).sum(-1)
         er = (h * self.attn_r).sum(-1)
         if self.fused_attention:
@@ -335,6 +355,29 @@ class MaxKGATConv(nn.Module):
         if self.bias is not None:
             rst = rst + self.bias
         return rst
+
+    def _forward_heads(self, csr: CSRGraph, h: torch.Tensor) -> torch.Tensor:
+        """``num_heads = H > 1``: ``[N, H, out_feats]`` as ``dglnn.GATConv`` returns it. The scores
+        are head-major ``[H, N]``, the attention is the head-batched fused kernel, MaxK keeps
+        ``maxk`` of the whole ``H * out_feats`` row, and one multi-head aggregation weighs every
+        kept feature by its own head's ``alpha``."""
+        H, F_ = self.num_heads, self.out_feats
+        hv = h.view(-1, H, F_)
+        el = (hv * self.attn_l).sum(-1).t()
+        er = (hv * self.attn_r).sum(-1).t()
+        alpha = gat_attention_heads(csr, el, er, self.negative_slope)
+        if self.attn_drop > 0:
+            alpha = F.dropout(alpha, self.attn_drop, self.training)
+        if self.feat_drop > 0 and self.training and not self.fused_dropout:
+            sp_data, sp_index = maxk(h, self.maxk, self.topk_mode)
+            sp_data = _sparse_dropout(sp_data, self.feat_drop, self.training)
+            rst = heads_aggregate(csr, alpha, sp_data, sp_index, H * F_)
+        else:
+            rst = maxk_heads_aggregate(h, csr, alpha, self.maxk, self.topk_mode,
+                                       dropout_p=self.feat_drop, training=self.training)
+        if self.bias is not None:
+            rst = rst + self.bias
+        return rst.view(-1, H, F_)
 
 
 class MaxKGINConv(nn.Module):

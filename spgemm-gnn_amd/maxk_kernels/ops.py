@@ -892,6 +892,175 @@ def edge_colsum(ptr_t, order, values, out: Optional[torch.Tensor] = None) -> tor
     return out
 
 
+# -------------------------------------------------------------------------------------
+# Multi-head attention and aggregation (include/maxk_hip.h, "GAT attention, heads" and
+# "Multi-head aggregation"); every per-head array is head-major
+# -------------------------------------------------------------------------------------
+def _matrix(t, name: str, rows, cols, shape_name: str, dev) -> None:
+    """A contiguous f32 ``[rows, cols]`` tensor (``None``: any extent) on ``dev``."""
+    _check_tensor(t, name, torch.float32)
+    _need(t.dim() == 2 and (rows is None or t.shape[0] == rows) and
+          (cols is None or t.shape[1] == cols), f"{name} must be [{shape_name}]")
+    _need(t.device == dev, "all tensors must be on the same device")
+
+
+def _out_matrix(out, name: str, rows: int, cols: int, shape_name: str, dev) -> torch.Tensor:
+    if out is None:
+        return torch.empty((rows, cols), dtype=torch.float32, device=dev)
+    _matrix(out, name, rows, cols, shape_name, dev)
+    return out
+
+
+def _gat_heads_args(ptr, idx, el, er):
+    """``ptr`` int32 ``[num_rows + 1]``, ``idx`` int32 ``[num_edges]``, ``el`` f32 ``[H,
+    num_cols]``, ``er`` f32 ``[H, num_rows]``. Returns ``(H, num_rows, num_cols, num_edges)``."""
+    _check_tensor(ptr, "ptr", torch.int32)
+    _need(ptr.dim() == 1 and ptr.numel() >= 1, "ptr must have num_rows+1 entries")
+    dev = ptr.device
+    _vector(idx, "idx", torch.int32, None, "num_edges", dev)
+    _matrix(el, "el", None, None, "num_heads, num_cols", dev)
+    _need(el.shape[0] >= 1, "el must have at least one head")
+    _matrix(er, "er", el.shape[0], ptr.numel() - 1, "num_heads, num_rows", dev)
+    return el.shape[0], ptr.numel() - 1, el.shape[1], idx.numel()
+
+
+def gat_attention_heads(ptr, idx, el, er, negative_slope: float,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`gat_attention` for ``H`` heads in one launch: ``el`` f32 ``[H, num_cols]``, ``er``
+    f32 ``[H, num_rows]``, the result ``alpha`` f32 ``[H, num_edges]``; row ``h`` is the
+    single-head call on row ``h`` bit for bit (``maxk_gat_attention_forward_heads``)."""
+    h, n, c, e = _gat_heads_args(ptr, idx, el, er)
+    out = _out_matrix(out, "out", h, e, "num_heads, num_edges", ptr.device)
+    with _device(ptr.device):
+        check(lib.maxk_gat_attention_forward_heads(_p(ptr), _p(idx), _p(el), _p(er),
+                                                   float(negative_slope), _p(out), h, n, c, e,
+                                                   _stream()), "gat_attention_heads")
+    return out
+
+
+def gat_attention_backward_heads(ptr, idx, el, er, negative_slope: float, alpha, grad_alpha,
+                                 out=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(grad_edge [H, num_edges], grad_er [H, num_rows])`` of :func:`gat_attention_heads`
+    (``maxk_gat_attention_backward_heads``); ``grad_el`` is :func:`edge_colsum_heads` of
+    ``grad_edge``."""
+    h, n, c, e = _gat_heads_args(ptr, idx, el, er)
+    dev = ptr.device
+    _matrix(alpha, "alpha", h, e, "num_heads, num_edges", dev)
+    _matrix(grad_alpha, "grad_alpha", h, e, "num_heads, num_edges", dev)
+    grad_edge, grad_er = out if out is not None else (None, None)
+    grad_edge = _out_matrix(grad_edge, "out[0]", h, e, "num_heads, num_edges", dev)
+    grad_er = _out_matrix(grad_er, "out[1]", h, n, "num_heads, num_rows", dev)
+    with _device(dev):
+        check(lib.maxk_gat_attention_backward_heads(_p(ptr), _p(idx), _p(el), _p(er),
+                                                    float(negative_slope), _p(alpha),
+                                                    _p(grad_alpha), _p(grad_edge), _p(grad_er), h,
+                                                    n, c, e, _stream()),
+              "gat_attention_backward_heads")
+    return grad_edge, grad_er
+
+
+def edge_colsum_heads(ptr_t, order, values, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`edge_colsum` of ``values`` f32 ``[H, num_edges]`` per head: f32 ``[H, num_cols]``
+    (``maxk_edge_colsum_heads``)."""
+    _check_tensor(ptr_t, "ptr_t", torch.int32)
+    _need(ptr_t.dim() == 1 and ptr_t.numel() >= 1, "ptr_t must have num_cols+1 entries")
+    dev = ptr_t.device
+    _vector(order, "order", torch.int32, None, "num_edges", dev)
+    _matrix(values, "values", None, order.numel(), "num_heads, num_edges", dev)
+    _need(values.shape[0] >= 1, "values must have at least one head")
+    h, c = values.shape[0], ptr_t.numel() - 1
+    out = _out_matrix(out, "out", h, c, "num_heads, num_cols", dev)
+    with _device(dev):
+        check(lib.maxk_edge_colsum_heads(_p(ptr_t), _p(order), _p(values), _p(out), h, c,
+                                         order.numel(), _stream()), "edge_colsum_heads")
+    return out
+
+
+def _heads_tables(sp_data, sp_index, dev):
+    """The plain CBSR tables ``[num_cols, k]`` (rows may be strided): ``(num_cols, k, ds, is)``."""
+    _need(isinstance(sp_data, torch.Tensor) and sp_data.dim() == 2,
+          "sp_data must be [num_cols, dim_k]")
+    num_cols, k = sp_data.shape
+    ds = _table(sp_data, "sp_data", torch.float32, num_cols, k)
+    is_ = _table(sp_index, "sp_index", torch.uint8, num_cols, k)
+    _need(sp_data.device == dev and sp_index.device == dev,
+          "all tensors must be on the same device")
+    return num_cols, k, ds, is_
+
+
+def heads_aggregate(ptr, idx, alpha, sp_data, sp_index, dim_origin: int,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Multi-head weighted aggregation of CBSR features, f32 ``[num_rows, dim_origin]``:
+    ``out[r, s] = sum_e alpha[s // F, e] * X[idx[e], s]`` over row ``r``'s edges, with ``alpha``
+    f32 ``[H, num_edges]`` head-major, ``F = dim_origin // H`` and ``X`` the densified tables
+    (``maxk_heads_aggregate_forward``; contract in include/maxk_hip.h, "Multi-head
+    aggregation"). No plan is built or used."""
+    _check_tensor(ptr, "ptr", torch.int32)
+    _need(ptr.dim() == 1 and ptr.numel() >= 1, "ptr must have num_rows+1 entries")
+    dev = ptr.device
+    _vector(idx, "idx", torch.int32, None, "num_edges", dev)
+    e, n = idx.numel(), ptr.numel() - 1
+    _matrix(alpha, "alpha", None, e, "num_heads, num_edges", dev)
+    h = alpha.shape[0]
+    _need(1 <= h and int(dim_origin) % max(h, 1) == 0,
+          "the number of heads (alpha.shape[0]) must divide dim_origin")
+    num_cols, k, ds, is_ = _heads_tables(sp_data, sp_index, dev)
+    _need(1 <= k <= dim_origin <= 256, "k must be between 1 and input dimension")
+    out = _out_matrix(out, "out", n, int(dim_origin), "num_rows, dim_origin", dev)
+    with _device(dev):
+        check(lib.maxk_heads_aggregate_forward(_p(ptr), _p(idx), _p(alpha), _p(sp_data), ds,
+                                               _p(sp_index), is_, _p(out), h, n, num_cols, e,
+                                               int(dim_origin), k, _stream()), "heads_aggregate")
+    return out
+
+
+def heads_aggregate_backward(ptr_t, idx_t, order, alpha, grad_out, sp_data, sp_index,
+                             need_sp: bool = True, need_alpha: bool = True):
+    """``(grad_sp [num_cols, k] or None, grad_alpha [H, num_edges] or None)`` of
+    :func:`heads_aggregate` from one gather of ``grad_out`` (f32 ``[num_rows, dim_origin]``, rows
+    may be strided) over the transposed structure ``(ptr_t, idx_t, order)``, all int32
+    (``maxk_heads_aggregate_backward``). A half that is not needed is not computed; nothing is
+    launched when neither is."""
+    _check_tensor(ptr_t, "ptr_t", torch.int32)
+    _need(ptr_t.dim() == 1 and ptr_t.numel() >= 1, "ptr_t must have num_cols+1 entries")
+    dev = ptr_t.device
+    _vector(order, "order", torch.int32, None, "num_edges", dev)
+    e = order.numel()
+    _vector(idx_t, "idx_t", torch.int32, e, "num_edges", dev)
+    _matrix(alpha, "alpha", None, e, "num_heads, num_edges", dev)
+    h = alpha.shape[0]
+    _need(isinstance(grad_out, torch.Tensor) and grad_out.dim() == 2,
+          "grad_out must be [num_rows, dim_origin]")
+    n, d = grad_out.shape
+    gs = _table(grad_out, "grad_out", torch.float32, n, d)
+    _need(grad_out.device == dev, "all tensors must be on the same device")
+    _need(1 <= h and d % max(h, 1) == 0,
+          "the number of heads (alpha.shape[0]) must divide dim_origin")
+    num_cols, k, ds, is_ = _heads_tables(sp_data, sp_index, dev)
+    _need(num_cols == ptr_t.numel() - 1, "sp_data must have num_cols rows")
+    _need(1 <= k <= d <= 256, "k must be between 1 and input dimension")
+    grad_sp = torch.empty((num_cols, k), dtype=torch.float32, device=dev) if need_sp else None
+    grad_alpha = torch.empty((h, e), dtype=torch.float32, device=dev) if need_alpha else None
+    if need_sp or need_alpha:
+        with _device(dev):
+            check(lib.maxk_heads_aggregate_backward(_p(ptr_t), _p(idx_t), _p(order), _p(alpha),
+                                                    _p(grad_out), gs, _p(sp_data), ds,
+                                                    _p(sp_index), is_, _p(grad_sp),
+                                                    _p(grad_alpha), h, n, num_cols, e, d, k,
+                                                    _stream()), "heads_aggregate_backward")
+    return grad_sp, grad_alpha
+
+
+def heads_row_limits() -> Tuple[int, ...]:
+    """``(row_short, row_medium, col_short, col_medium)``: the row lengths at which the
+    multi-head forward and the column lengths at which its backward switch regime
+    (``maxk_heads_row_limits``); exactly a limit's length runs in the regime below it."""
+    count = lib.maxk_heads_row_limits(None, 0)
+    buf = (ctypes.c_int32 * count)()
+    lib.maxk_heads_row_limits(ctypes.cast(buf, ctypes.c_void_p), count)
+    return tuple(int(v) for v in buf)
+
+
 def plan_col_order(plan: GraphPlan) -> torch.Tensor:
     """The plan's column order: int32 [num_cols], position -> column of the backward's column
     blocks (the identity for plans without one)."""

@@ -8,6 +8,8 @@
                                          (rocprofv3 --kernel-trace --stats), in the same form
   tools/kernel_list.py --launched CSV.. --diff FIXTURE
                                          both differences against a list; exit 1 unless equal
+  --namespace PREFIX                     keep the names that start with PREFIX instead of maxk::
+                                         (maxk_mh:: -> tests/golden/kernel_instantiations_heads.txt)
 
 The compiled set comes from the host stub symbols (`__device_stub__`) in the library's symbol
 table, read with llvm-readelf and demangled with c++filt; kernels outside namespace maxk
@@ -58,12 +60,15 @@ def strip_params(name):
     return name
 
 
-def ours(names):
-    return sorted({n for n in map(strip_params, names) if n.startswith("maxk::")})
+DEFAULT_PREFIX = "maxk::"
 
 
-def compiled(lib=DEFAULT_LIB, readelf=None):
-    """Sorted names of the maxk:: kernel instantiations in `lib`."""
+def ours(names, prefix=DEFAULT_PREFIX):
+    return sorted({n for n in map(strip_params, names) if n.startswith(prefix)})
+
+
+def compiled(lib=DEFAULT_LIB, readelf=None, prefix=DEFAULT_PREFIX):
+    """Sorted names of the kernel instantiations of namespace `prefix` (maxk::) in `lib`."""
     readelf = readelf or find_readelf()
     if readelf is None:
         raise FileNotFoundError("llvm-readelf not found")
@@ -73,10 +78,10 @@ def compiled(lib=DEFAULT_LIB, readelf=None):
                       if STUB in w})
     dem = subprocess.run(["c++filt"], input="\n".join(mangled) + "\n", check=True,
                          capture_output=True, text=True).stdout
-    return ours(n.replace(STUB, "") for n in dem.splitlines() if n.strip())
+    return ours((n.replace(STUB, "") for n in dem.splitlines() if n.strip()), prefix)
 
 
-def launched(csv_path):
+def launched(csv_path, prefix=DEFAULT_PREFIX):
     """Sorted maxk:: kernel names of a kernel-stats CSV (column "Name", else the first)."""
     with open(csv_path, newline="") as f:
         rows = list(csv.reader(f))
@@ -85,7 +90,7 @@ def launched(csv_path):
     head = [h.strip().strip('"') for h in rows[0]]
     col = head.index("Name") if "Name" in head else head.index("KernelName") \
         if "KernelName" in head else 0
-    return ours(r[col] for r in rows[1:] if len(r) > col)
+    return ours((r[col] for r in rows[1:] if len(r) > col), prefix)
 
 
 def read_list(path):
@@ -99,11 +104,13 @@ def main(argv=None):
     ap.add_argument("--launched", metavar="CSV", nargs="+",
                     help="kernel-stats CSVs of traced runs (several: the union)")
     ap.add_argument("--diff", metavar="LIST", help="compare with a list of names")
+    ap.add_argument("--namespace", metavar="PREFIX", default=DEFAULT_PREFIX,
+                    help="keep the names that start with PREFIX (default maxk::)")
     a = ap.parse_args(argv)
     if a.launched:
-        names = sorted({n for path in a.launched for n in launched(path)})
+        names = sorted({n for path in a.launched for n in launched(path, a.namespace)})
     else:
-        names = compiled(a.lib)
+        names = compiled(a.lib, prefix=a.namespace)
     if not a.diff:
         print("\n".join(names))
         return 0
