@@ -24,6 +24,7 @@ from .ops import (  # noqa: F401
     edge_softmax_row_limits,
     get_plan,
     heads_row_limits,
+    max_row_limits,
     maxk_backward,
     maxk_forward,
     plan_col_order,
@@ -59,6 +60,12 @@ from .heads import (  # noqa: F401,E402  (and its operators)
     heads_aggregate,
     maxk_heads_aggregate,
 )
+from .pooling import (  # noqa: F401,E402  (and its operators)
+    MaxAggregateFunction,
+    dense_max_aggregate,
+    max_aggregate,
+    maxk_max_aggregate,
+)
 from .layers import (  # noqa: F401,E402
     MaxKGCN,
     MaxKGATConv,
@@ -80,6 +87,8 @@ __all__ = [
     "MaxKGATConv", "gat_attention", "GATAttentionFunction",
     "gat_attention_heads", "GATAttentionHeadsFunction", "heads_aggregate", "maxk_heads_aggregate",
     "HeadsAggregateFunction", "heads_row_limits",
+    "max_aggregate", "maxk_max_aggregate", "dense_max_aggregate", "MaxAggregateFunction",
+    "max_row_limits",
 ]
 
 ABI_VERSION = lib.maxk_abi_version()

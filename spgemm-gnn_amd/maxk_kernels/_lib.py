@@ -104,6 +104,11 @@ SIGNATURES = {
                                                      _i64, _vp, _vp, _i32, _i32, _i32, _i64, _i32,
                                                      _i32, _vp]),
     "maxk_heads_row_limits": (ctypes.c_int, [_vp, _i32]),
+    "maxk_max_aggregate_forward": (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp,
+                                                  _i32, _i32, _i64, _i32, _i32, _vp]),
+    "maxk_max_aggregate_backward": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64,
+                                                   _vp, _i32, _i32, _i64, _i32, _i32, _vp]),
+    "maxk_max_row_limits": (ctypes.c_int, [_vp, _i32]),
     "maxk_dense_spmm_csr": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "maxk_warp4_build": (ctypes.c_int, [_vp, _i32, _i32, _vp, _i64, ctypes.POINTER(_i64)]),
 }

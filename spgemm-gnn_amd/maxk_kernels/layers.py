@@ -20,7 +20,13 @@ utils/models.py:109-411 + dglnn.SAGEConv / GraphConv / GINConv):
     ``norm``; ``x = feat_drop(MaxK(feat))``. Dropout acts on the k kept values only (the
     other entries are zero either way). The reference's layer applies MaxK after
     ``fc_neigh`` and dropout to its output (maxk_layers.py:85-88,183);
-    ``maxk_after_fc=True`` keeps that ordering.
+    ``maxk_after_fc=True`` keeps that ordering. ``aggregator_type="pool"``:
+    ``rst = fc_self(x) + fc_neigh(max_{u->v} MaxK(fc_pool(x_u)))``, MaxK in the place of
+    DGL's ReLU after ``fc_pool`` and the max taken by the max-aggregation kernels
+    (:mod:`maxk_kernels.pooling`; ``nonlinear="relu"``: ``max ReLU(fc_pool(x_u))`` on dense
+    rows, the same kernels with ``k = D``); it takes no ``edge_weight``.
+    ``aggregator_type="gcn"``: ``rst = fc_neigh((sum_{u->v} x_u + x_v) / (in_deg_v + 1))``
+    without ``fc_self``, as in DGL.
   - ``MaxKGCNConv``: ``rst = A_norm MaxK(feat W) (+ bias)`` with ``A_norm`` the GraphConv
     normalisation ('both', 'right', 'left', 'none'); with ``weight=False`` this is
     ``dglnn.GraphConv(weight=None)`` applied to ``MaxK(feat)``.
@@ -78,6 +84,7 @@ from .autograd import (CSRGraph, dense_aggregate, densify, edge_softmax, maxk, m
                        maxk_self_aggregate, spgemm)
 from .attention import gat_attention
 from .heads import gat_attention_heads, heads_aggregate, maxk_heads_aggregate
+from .pooling import dense_max_aggregate, maxk_max_aggregate
 
 NONLINEAR = ("maxk", "relu")
 
@@ -149,8 +156,10 @@ class MaxKSAGEConv(nn.Module):
                  nonlinear="maxk", fused_dropout=False):
         super().__init__()
         self.fused_dropout = bool(fused_dropout)
-        if aggregator_type not in ("mean", "sum"):
+        if aggregator_type not in ("mean", "sum", "pool", "gcn"):
             raise ValueError(f"Unsupported aggregator type: {aggregator_type}")
+        if maxk_after_fc and aggregator_type in ("pool", "gcn"):
+            raise ValueError(f"maxk_after_fc is not defined for the {aggregator_type} aggregator")
         self.in_feats = in_feats
         self.out_feats = out_feats
         self.aggregator_type = aggregator_type
@@ -158,22 +167,62 @@ class MaxKSAGEConv(nn.Module):
         self.maxk_after_fc = maxk_after_fc
         self.topk_mode = topk_mode
         self.nonlinear = _check_nonlinear(nonlinear)
-        self.fc_self = nn.Linear(in_feats, out_feats, bias=False)
+        if aggregator_type != "gcn":  # DGL's gcn aggregator has no self weight
+            self.fc_self = nn.Linear(in_feats, out_feats, bias=False)
         self.fc_neigh = nn.Linear(in_feats, out_feats, bias=False)
         self.bias = nn.Parameter(torch.zeros(out_feats)) if bias else None
         self.norm = _make_norm(norm, out_feats)
         self.feat_drop = float(feat_drop)
+        if aggregator_type == "pool":  # after the existing parameters: their stream is unchanged
+            self.fc_pool = nn.Linear(in_feats, in_feats)
         self.reset_parameters()
 
     def reset_parameters(self):
         gain = nn.init.calculate_gain("relu")
-        nn.init.xavier_uniform_(self.fc_self.weight, gain=gain)
+        if self.aggregator_type != "gcn":
+            nn.init.xavier_uniform_(self.fc_self.weight, gain=gain)
         nn.init.xavier_uniform_(self.fc_neigh.weight, gain=gain)
         if self.bias is not None:
             nn.init.zeros_(self.bias)
+        if self.aggregator_type == "pool":
+            nn.init.xavier_uniform_(self.fc_pool.weight, gain=gain)
+
+    def _forward_pool(self, graph, feat: torch.Tensor, edge_weight) -> torch.Tensor:
+        """dglnn.SAGEConv("pool"): ``fc_self(x) + fc_neigh(max_{u->v} act(fc_pool(x_u)))`` with
+        MaxK in the place of DGL's ReLU on the ``nonlinear="maxk"`` path."""
+        if edge_weight is not None:
+            raise NotImplementedError("the pool aggregator takes no edge_weight (a weighted max "
+                                      "is not defined here)")
+        csr = as_csr(graph)
+        if self.nonlinear == "relu":
+            x = F.dropout(feat, self.feat_drop, self.training) if self.feat_drop > 0 else feat
+            neigh = dense_max_aggregate(F.relu(self.fc_pool(x)), csr)
+        else:
+            sp_data, sp_index = _maxk_dropout(self, feat)
+            x = densify(sp_data, sp_index, self.in_feats)
+            neigh = maxk_max_aggregate(self.fc_pool(x), csr, self.maxk, self.topk_mode)
+        return self.fc_self(x) + self.fc_neigh(neigh)
+
+    def _forward_gcn(self, graph, feat: torch.Tensor, ew) -> torch.Tensor:
+        """dglnn.SAGEConv("gcn"): ``fc_neigh((sum_{u->v} x_u + x_v) / (in_deg_v + 1))``;
+        ``edge_weight`` multiplies the messages only."""
+        csr = as_csr(graph, ew).with_values("sum")
+        if self.nonlinear == "relu":
+            x = F.dropout(feat, self.feat_drop, self.training) if self.feat_drop > 0 else feat
+            neigh = dense_aggregate(x, csr, ew)
+        else:
+            x, neigh = _maxk_self_pair(self, feat, csr, ew)
+        deg = (csr.in_degrees() + 1).to(feat.dtype).unsqueeze(1)
+        return self.fc_neigh((neigh + x) / deg)
 
     def forward(self, graph, feat: torch.Tensor, edge_weight=None) -> torch.Tensor:
         ew = edge_weight
+        if self.aggregator_type in ("pool", "gcn"):
+            rst = (self._forward_pool if self.aggregator_type == "pool"
+                   else self._forward_gcn)(graph, feat, ew)
+            if self.bias is not None:
+                rst = rst + self.bias
+            return self.norm(rst) if self.norm is not None else rst
         csr = as_csr(graph, ew).with_values(self.aggregator_type)
         if self.nonlinear == "relu":
             # dglnn.SAGEConv(mean) on dense features (the model applied the ReLU)
@@ -417,14 +466,14 @@ class MaxKSAGE(nn.Module):
     ``nonlinear='relu'`` the utils/models.py:109-165 SAGE: ReLU, then dglnn.SAGEConv(mean)."""
 
     def __init__(self, in_size, hid_size, num_hid_layers, out_size, maxk=32, feat_drop=0.5,
-                 norm=False, nonlinear="maxk", fused_dropout=False):
+                 norm=False, nonlinear="maxk", fused_dropout=False, aggregator_type="mean"):
         super().__init__()
         self.nonlinear = _check_nonlinear(nonlinear)
         self.num_layers = num_hid_layers
         self.lin_in = nn.Linear(in_size, hid_size)
         self.lin_out = nn.Linear(hid_size, out_size)
         self.layers = nn.ModuleList(
-            MaxKSAGEConv(hid_size, hid_size, "mean", feat_drop=feat_drop,
+            MaxKSAGEConv(hid_size, hid_size, aggregator_type, feat_drop=feat_drop,
                          norm=nn.LayerNorm(hid_size) if norm else None, maxk=maxk,
                          nonlinear=nonlinear, fused_dropout=fused_dropout)
             for _ in range(num_hid_layers))

@@ -1061,6 +1061,83 @@ def heads_row_limits() -> Tuple[int, ...]:
     return tuple(int(v) for v in buf)
 
 
+# -------------------------------------------------------------------------------------
+# Max aggregation (include/maxk_hip.h, "Max aggregation")
+# -------------------------------------------------------------------------------------
+MAX_ROW_EDGES = 1 << 24  # the forward's precondition: every row is shorter than this
+
+
+def max_aggregate_forward(ptr, idx, sp_data, sp_index, dim_origin: int, with_arg: bool = True):
+    """``(out f32, arg_edge int32 or None, arg_slot u8 or None)``, each ``[num_rows,
+    dim_origin]``: the element-wise maximum of the densified CBSR rows of each row's in-edges,
+    unselected features as implicit zeros, and the winner's CSR edge and slot (``-1``, ``0`` for
+    the implicit zero). ``with_arg=False`` writes ``out`` alone, with the same bits
+    (``maxk_max_aggregate_forward``). Rows of 2^24 edges or more are not supported and not
+    checked here (:func:`maxk_kernels.max_aggregate` checks its graph once)."""
+    _check_tensor(ptr, "ptr", torch.int32)
+    _need(ptr.dim() == 1 and ptr.numel() >= 1, "ptr must have num_rows+1 entries")
+    dev = ptr.device
+    _vector(idx, "idx", torch.int32, None, "num_edges", dev)
+    e, n = idx.numel(), ptr.numel() - 1
+    num_cols, k, ds, is_ = _heads_tables(sp_data, sp_index, dev)
+    d = int(dim_origin)
+    _need(1 <= k <= d <= 256, "k must be between 1 and input dimension")
+    out = torch.empty((n, d), dtype=torch.float32, device=dev)
+    arg_edge = torch.empty((n, d), dtype=torch.int32, device=dev) if with_arg else None
+    arg_slot = torch.empty((n, d), dtype=torch.uint8, device=dev) if with_arg else None
+    with _device(dev):
+        check(lib.maxk_max_aggregate_forward(_p(ptr), _p(idx), _p(sp_data), ds, _p(sp_index), is_,
+                                             _p(out), _p(arg_edge), _p(arg_slot), n, num_cols, e,
+                                             d, k, _stream()), "max_aggregate_forward")
+    return out, arg_edge, arg_slot
+
+
+def max_aggregate_backward(ptr_t, idx_t, order, grad_out, arg_edge, arg_slot,
+                           sp_index) -> torch.Tensor:
+    """``grad_sp [num_cols, k]`` of :func:`max_aggregate_forward`: each ``grad_out`` element
+    (f32 ``[num_rows, dim_origin]``, rows may be strided) goes to the slot that ``arg_edge`` /
+    ``arg_slot`` name, summed per slot over the transposed structure ``(ptr_t, idx_t, order)``,
+    all int32 (``maxk_max_aggregate_backward``)."""
+    _check_tensor(ptr_t, "ptr_t", torch.int32)
+    _need(ptr_t.dim() == 1 and ptr_t.numel() >= 1, "ptr_t must have num_cols+1 entries")
+    dev = ptr_t.device
+    _vector(order, "order", torch.int32, None, "num_edges", dev)
+    e = order.numel()
+    _vector(idx_t, "idx_t", torch.int32, e, "num_edges", dev)
+    _need(isinstance(grad_out, torch.Tensor) and grad_out.dim() == 2,
+          "grad_out must be [num_rows, dim_origin]")
+    n, d = grad_out.shape
+    gs = _table(grad_out, "grad_out", torch.float32, n, d)
+    _need(grad_out.device == dev, "all tensors must be on the same device")
+    for t, name, dtype in ((arg_edge, "arg_edge", torch.int32), (arg_slot, "arg_slot", torch.uint8)):
+        _check_tensor(t, name, dtype)
+        _need(tuple(t.shape) == (n, d) and t.device == dev,
+              f"{name} must be [num_rows, dim_origin] on the same device")
+    _need(isinstance(sp_index, torch.Tensor) and sp_index.dim() == 2,
+          "sp_index must be [num_cols, dim_k]")
+    num_cols, k = sp_index.shape
+    is_ = _table(sp_index, "sp_index", torch.uint8, num_cols, k)
+    _need(sp_index.device == dev, "all tensors must be on the same device")
+    _need(num_cols == ptr_t.numel() - 1, "sp_index must have num_cols rows")
+    _need(1 <= k <= d <= 256, "k must be between 1 and input dimension")
+    grad_sp = torch.empty((num_cols, k), dtype=torch.float32, device=dev)
+    with _device(dev):
+        check(lib.maxk_max_aggregate_backward(_p(ptr_t), _p(idx_t), _p(order), _p(grad_out), gs,
+                                              _p(arg_edge), _p(arg_slot), _p(sp_index), is_,
+                                              _p(grad_sp), n, num_cols, e, d, k, _stream()),
+              "max_aggregate_backward")
+    return grad_sp
+
+
+def max_row_limits() -> Tuple[int, ...]:
+    """``(row_short, row_medium, col_short, col_medium)`` of the max aggregation's forward and
+    backward (``maxk_max_row_limits``); exactly a limit's length runs in the regime below it."""
+    count = lib.maxk_max_row_limits(None, 0)
+    buf = (ctypes.c_int32 * count)()
+    lib.maxk_max_row_limits(ctypes.cast(buf, ctypes.c_void_p), count)
+    return tuple(int(v) for v in buf)
+
+
 def plan_col_order(plan: GraphPlan) -> torch.Tensor:
     """The plan's column order: int32 [num_cols], position -> column of the backward's column
     blocks (the identity for plans without one)."""
