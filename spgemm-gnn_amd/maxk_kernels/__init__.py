@@ -28,6 +28,7 @@ from .ops import (  # noqa: F401
     maxk_backward,
     maxk_forward,
     plan_col_order,
+    sample_row_limits,
     spgemm_backward,
     spgemm_edge_grad,
     spgemm_forward,
@@ -66,6 +67,17 @@ from .pooling import (  # noqa: F401,E402  (and its operators)
     max_aggregate,
     maxk_max_aggregate,
 )
+from .sampling import (  # noqa: F401,E402
+    Block,
+    NeighborSampler,
+    block_aggregate,
+    block_compact,
+    block_self_aggregate,
+    block_spgemm,
+    layer_seed,
+    sample_neighbors,
+    to_block,
+)
 from .layers import (  # noqa: F401,E402
     MaxKGCN,
     MaxKGATConv,
@@ -89,6 +101,8 @@ __all__ = [
     "HeadsAggregateFunction", "heads_row_limits",
     "max_aggregate", "maxk_max_aggregate", "dense_max_aggregate", "MaxAggregateFunction",
     "max_row_limits",
+    "sample_neighbors", "block_compact", "Block", "to_block", "NeighborSampler", "layer_seed",
+    "block_aggregate", "block_self_aggregate", "block_spgemm", "sample_row_limits",
 ]
 
 ABI_VERSION = lib.maxk_abi_version()

@@ -109,6 +109,13 @@ SIGNATURES = {
     "maxk_max_aggregate_backward": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64,
                                                    _vp, _i32, _i32, _i64, _i32, _i32, _vp]),
     "maxk_max_row_limits": (ctypes.c_int, [_vp, _i32]),
+    "maxk_sample_scratch_bytes": (ctypes.c_int64, [_i32]),
+    "maxk_sample_neighbors": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32,
+                                             _i64, _i32, _i32, ctypes.c_uint64, _vp]),
+    "maxk_sample_row_limits": (ctypes.c_int, [_vp, _i32]),
+    "maxk_block_compact_scratch_bytes": (ctypes.c_int64, [_i32]),
+    "maxk_block_compact": (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i64,
+                                          _i32, _vp]),
     "maxk_dense_spmm_csr": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "maxk_warp4_build": (ctypes.c_int, [_vp, _i32, _i32, _vp, _i64, ctypes.POINTER(_i64)]),
 }

@@ -70,6 +70,13 @@ and the output is differentiable in it, on both nonlinear paths: the SDDMM kerne
 the dense features with identity selectors. It needs a CSRGraph: with a DGL graph it raises
 ``TypeError``, because the edge-id permutation between the two orders is not mapped.
 
+Sampled blocks (:mod:`maxk_kernels.sampling`): ``MaxKSAGEConv.forward(block, feat)`` takes
+``feat [num_src, in]`` to ``[num_dst, out]`` for the ``mean`` and ``sum`` aggregators on both
+``nonlinear`` paths, with the neighbour term over the block's sampled edges and the self term from
+the first ``num_dst`` rows of the masked input; ``MaxKSAGE.forward(blocks, x)`` takes one block
+per layer, outermost first. Every other aggregator, layer and model, and ``edge_weight=``, raise
+``NotImplementedError`` for a block.
+
 ``MaxKGATConv`` is the layer that ``edge_weight=`` and the edge softmax (``edge_softmax``,
 ``maxk_edge_softmax_forward`` / ``_backward``) make possible: single-head graph attention
 (``dglnn.GATConv`` with one head) whose messages are the MaxK features.
@@ -85,6 +92,7 @@ from .autograd import (CSRGraph, dense_aggregate, densify, edge_softmax, maxk, m
 from .attention import gat_attention
 from .heads import gat_attention_heads, heads_aggregate, maxk_heads_aggregate
 from .pooling import dense_max_aggregate, maxk_max_aggregate
+from .sampling import Block, block_aggregate, block_self_aggregate, block_spgemm
 
 NONLINEAR = ("maxk", "relu")
 
@@ -98,6 +106,17 @@ def as_csr(graph, edge_weight=None) -> CSRGraph:
     if hasattr(graph, "adj_tensors"):
         return CSRGraph.from_dgl(graph)
     raise TypeError("graph must be a maxk_kernels.CSRGraph or a DGL graph")
+
+
+BLOCK_SUPPORT = ("sampled blocks are supported by MaxKSAGEConv and MaxKSAGE with "
+                 'aggregator_type "mean" or "sum", without edge_weight')
+
+
+def _refuse_block(graph, who: str) -> None:
+    """Layers without a block path refuse a Block (or a list of them) by name."""
+    if isinstance(graph, Block) or (isinstance(graph, (list, tuple)) and graph and
+                                    all(isinstance(b, Block) for b in graph)):
+        raise NotImplementedError(f"{who} does not take a Block: {BLOCK_SUPPORT}")
 
 
 def _check_nonlinear(nonlinear: str) -> str:
@@ -215,8 +234,50 @@ class MaxKSAGEConv(nn.Module):
         deg = (csr.in_degrees() + 1).to(feat.dtype).unsqueeze(1)
         return self.fc_neigh((neigh + x) / deg)
 
+    def _forward_block(self, block: Block, feat: torch.Tensor, edge_weight) -> torch.Tensor:
+        """``feat [num_src, in] -> [num_dst, out]`` on a sampled block: the neighbour term over
+        the sampled edges (``block_aggregate``: MaxK, then the plan-less weighted sum), the self
+        term from the first ``num_dst`` rows of the masked input."""
+        if self.aggregator_type not in ("mean", "sum"):
+            raise NotImplementedError(f'MaxKSAGEConv with aggregator_type "{self.aggregator_type}"'
+                                      f" does not take a Block: {BLOCK_SUPPORT}")
+        if edge_weight is not None:
+            raise NotImplementedError("MaxKSAGEConv with edge_weight does not take a Block: "
+                                      f"{BLOCK_SUPPORT}")
+        blk = block.with_values(self.aggregator_type)
+        nd = blk.num_dst
+        drop = self.feat_drop > 0 and self.training
+        if self.nonlinear == "relu":
+            # dense rows through the same kernels with k = D (identity selection)
+            x = F.dropout(feat, self.feat_drop, self.training) if self.feat_drop > 0 else feat
+            rst = self.fc_self(x[:nd]) + self.fc_neigh(block_aggregate(x, blk, x.shape[1]))
+        elif self.maxk_after_fc:
+            h_self = self.fc_self(feat[:nd])
+            if drop and not self.fused_dropout:
+                sp_data, sp_index = maxk(self.fc_neigh(feat), self.maxk, self.topk_mode)
+                sp_data = _sparse_dropout(sp_data, self.feat_drop, self.training)
+                rst = h_self + block_spgemm(sp_data, sp_index, blk, self.out_feats)
+            else:
+                rst = h_self + block_aggregate(self.fc_neigh(feat), blk, self.maxk,
+                                               self.topk_mode, dropout_p=self.feat_drop,
+                                               training=self.training)
+        else:
+            if drop and not self.fused_dropout:
+                sp_data, sp_index = _maxk_dropout(self, feat)
+                x = densify(sp_data, sp_index, self.in_feats)
+                neigh = block_spgemm(sp_data, sp_index, blk, self.in_feats)
+            else:
+                x, neigh = block_self_aggregate(feat, blk, self.maxk, self.topk_mode,
+                                                dropout_p=self.feat_drop, training=self.training)
+            rst = self.fc_self(x[:nd]) + self.fc_neigh(neigh)
+        if self.bias is not None:
+            rst = rst + self.bias
+        return self.norm(rst) if self.norm is not None else rst
+
     def forward(self, graph, feat: torch.Tensor, edge_weight=None) -> torch.Tensor:
         ew = edge_weight
+        if isinstance(graph, Block):
+            return self._forward_block(graph, feat, ew)
         if self.aggregator_type in ("pool", "gcn"):
             rst = (self._forward_pool if self.aggregator_type == "pool"
                    else self._forward_gcn)(graph, feat, ew)
@@ -282,6 +343,7 @@ class MaxKGCNConv(nn.Module):
             nn.init.zeros_(self.bias)
 
     def forward(self, graph, feat: torch.Tensor, edge_weight=None) -> torch.Tensor:
+        _refuse_block(graph, "MaxKGCNConv")
         ew = edge_weight
         csr = as_csr(graph, ew)
         if not self.allow_zero_in_degree and bool((csr.in_degrees() == 0).any()):
@@ -373,6 +435,7 @@ class MaxKGATConv(nn.Module):
             nn.init.zeros_(self.bias)
 
     def forward(self, graph, feat: torch.Tensor) -> torch.Tensor:
+        _refuse_block(graph, "MaxKGATConv")
         csr = as_csr(graph, True)  # attention weights are an edge_weight: CSRGraph only
         if not self.allow_zero_in_degree and bool((csr.in_degrees() == 0).any()):
             raise ValueError("Graph has nodes with zero in-degree")
@@ -453,6 +516,7 @@ class MaxKGINConv(nn.Module):
             self.register_buffer("eps", eps)
 
     def forward(self, graph, feat: torch.Tensor, edge_weight=None) -> torch.Tensor:
+        _refuse_block(graph, "MaxKGINConv")
         csr = as_csr(graph, edge_weight).with_values("sum")
         if self.nonlinear == "relu":
             x = F.dropout(feat, self.feat_drop, self.training) if self.feat_drop > 0 else feat
@@ -481,11 +545,17 @@ class MaxKSAGE(nn.Module):
         nn.init.xavier_uniform_(self.lin_out.weight)
 
     def forward(self, g, x, edge_weight=None):
+        """``g``: a graph for every layer, or a list of sampled blocks, one per layer, outermost
+        first (``NeighborSampler.sample``): ``x`` then holds the rows ``blocks[0].src_ids`` and
+        the result the rows of the seeds."""
+        blocks = list(g) if isinstance(g, (list, tuple)) else None
+        if blocks is not None and len(blocks) != len(self.layers):
+            raise ValueError(f"MaxKSAGE has {len(self.layers)} layers, got {len(blocks)} blocks")
         x = self.lin_in(x)
-        for layer in self.layers:
+        for i, layer in enumerate(self.layers):
             if self.nonlinear == "relu":
                 x = F.relu(x)
-            x = layer(g, x, edge_weight)
+            x = layer(g if blocks is None else blocks[i], x, edge_weight)
         return self.lin_out(x)
 
 
@@ -513,6 +583,7 @@ class MaxKGCN(nn.Module):
             nn.init.xavier_uniform_(lin.weight)
 
     def forward(self, g, x, edge_weight=None):
+        _refuse_block(g, "MaxKGCN")
         x = self.lin_in(x).relu()
         for i, conv in enumerate(self.gcnlayers):
             x = self.linlayers[i](x)
@@ -547,6 +618,7 @@ class MaxKGIN(nn.Module):
             nn.init.xavier_uniform_(lin.weight)
 
     def forward(self, g, x, edge_weight=None):
+        _refuse_block(g, "MaxKGIN")
         x = self.lin_in(x).relu()
         for i, conv in enumerate(self.ginlayers):
             x = self.linlayers[i](x)

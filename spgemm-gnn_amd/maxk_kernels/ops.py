@@ -1138,6 +1138,105 @@ def max_row_limits() -> Tuple[int, ...]:
     return tuple(int(v) for v in buf)
 
 
+# -------------------------------------------------------------------------------------
+# Neighbour sampling (include/maxk_hip.h, "Neighbour sampling")
+# -------------------------------------------------------------------------------------
+def _scratch(scratch, nbytes: int, dev) -> torch.Tensor:
+    if scratch is None:
+        return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _check_tensor(scratch, "scratch", torch.uint8)
+    _need(scratch.dim() == 1 and scratch.numel() >= nbytes and scratch.device == dev,
+          f"scratch must be a u8 tensor of at least {nbytes} bytes on the same device")
+    return scratch
+
+
+def sample_capacity(num_edges: int, num_seeds: int, fanout: int) -> int:
+    """Entries of ``out_col`` / ``out_eid`` that hold every result of distinct seeds:
+    ``min(num_edges, num_seeds * fanout)``, ``num_edges`` for ``fanout < 0``."""
+    return int(num_edges) if fanout < 0 else min(int(num_edges), int(num_seeds) * int(fanout))
+
+
+def sample_neighbors(ptr, idx, seeds, fanout: int, seed: int, out=None, scratch=None):
+    """``(out_ptr int32 [S + 1], out_col int32 [capacity], out_eid int32 [capacity])``: at most
+    ``fanout`` in-edges of each seed row, chosen by the rank rule of the header, in ascending
+    edge number (``maxk_sample_neighbors``). The buffers come back whole: entries at and past
+    ``out_ptr[S]`` are not written, and nothing is read back here. ``out``: the three buffers,
+    pre-allocated (``capacity = out[1].numel()``; default :func:`sample_capacity`); ``scratch``: a
+    u8 buffer of :func:`sample_scratch_bytes` bytes. With both given the call allocates nothing
+    and can be captured into a graph."""
+    _check_tensor(ptr, "ptr", torch.int32)
+    _need(ptr.dim() == 1 and ptr.numel() >= 1, "ptr must have num_rows+1 entries")
+    dev = ptr.device
+    _vector(idx, "idx", torch.int32, None, "num_edges", dev)
+    _vector(seeds, "seeds", torch.int32, None, "num_seeds", dev)
+    n, e, s, fanout = ptr.numel() - 1, idx.numel(), seeds.numel(), int(fanout)
+    _need(fanout != 0, "fanout must be positive, or negative for every neighbour")
+    if out is None:
+        cap = sample_capacity(e, s, fanout)
+        out = (torch.empty(s + 1, dtype=torch.int32, device=dev),
+               torch.empty(cap, dtype=torch.int32, device=dev),
+               torch.empty(cap, dtype=torch.int32, device=dev))
+    out_ptr, out_col, out_eid = out
+    _vector(out_ptr, "out_ptr", torch.int32, s + 1, "num_seeds + 1", dev)
+    _vector(out_col, "out_col", torch.int32, None, "capacity", dev)
+    _vector(out_eid, "out_eid", torch.int32, out_col.numel(), "capacity", dev)
+    nbytes = sample_scratch_bytes(s)
+    scratch = _scratch(scratch, nbytes, dev)
+    with _device(dev):
+        check(lib.maxk_sample_neighbors(_p(ptr), _p(idx), _p(seeds), _p(out_ptr), _p(out_col),
+                                        _p(out_eid), out_col.numel(), _p(scratch),
+                                        scratch.numel(), n, e, s, fanout,
+                                        int(seed) & 0xFFFFFFFFFFFFFFFF, _stream()),
+              "sample_neighbors")
+    return out_ptr, out_col, out_eid
+
+
+def sample_scratch_bytes(num_seeds: int) -> int:
+    return int(lib.maxk_sample_scratch_bytes(int(num_seeds)))
+
+
+def block_compact_scratch_bytes(num_cols: int) -> int:
+    return int(lib.maxk_block_compact_scratch_bytes(int(num_cols)))
+
+
+def block_compact(seeds, cols, num_cols: int, out=None, scratch=None):
+    """``(src_ids int32 [capacity], local_col int32 [num_edges], counts int32 [2])``: the seeds,
+    then every other column of ``cols`` once in ascending order; ``cols`` mapped to positions in
+    ``src_ids``; ``counts = {num_src, distinct_seeds}`` on the device (``maxk_block_compact``).
+    ``src_ids`` comes back whole (``capacity = num_seeds + min(num_edges, num_cols)`` by default)
+    and nothing is read back here. ``out`` / ``scratch`` (:func:`block_compact_scratch_bytes`
+    bytes, u8) as for :func:`sample_neighbors`."""
+    _check_tensor(seeds, "seeds", torch.int32)
+    dev = seeds.device
+    _vector(seeds, "seeds", torch.int32, None, "num_seeds", dev)
+    _vector(cols, "cols", torch.int32, None, "num_edges", dev)
+    s, m, num_cols = seeds.numel(), cols.numel(), int(num_cols)
+    _need(num_cols >= 0, "num_cols must not be negative")
+    if out is None:
+        out = (torch.empty(s + min(m, num_cols), dtype=torch.int32, device=dev),
+               torch.empty(m, dtype=torch.int32, device=dev),
+               torch.empty(2, dtype=torch.int32, device=dev))
+    src_ids, local_col, counts = out
+    _vector(src_ids, "src_ids", torch.int32, None, "capacity", dev)
+    _vector(local_col, "local_col", torch.int32, m, "num_edges", dev)
+    _vector(counts, "counts", torch.int32, 2, "2", dev)
+    scratch = _scratch(scratch, block_compact_scratch_bytes(num_cols), dev)
+    with _device(dev):
+        check(lib.maxk_block_compact(_p(seeds), _p(cols), _p(src_ids), src_ids.numel(),
+                                     _p(local_col), _p(counts), _p(scratch), scratch.numel(), s,
+                                     m, num_cols, _stream()), "block_compact")
+    return src_ids, local_col, counts
+
+
+def sample_row_limits() -> Tuple[int, ...]:
+    """``(short, medium)``: the row lengths at which the sampler switches regime
+    (``maxk_sample_row_limits``); exactly a limit's length runs in the regime below it."""
+    count = lib.maxk_sample_row_limits(None, 0)
+    buf = (ctypes.c_int32 * count)()
+    lib.maxk_sample_row_limits(ctypes.cast(buf, ctypes.c_void_p), count)
+    return tuple(int(v) for v in buf)
+
+
 def plan_col_order(plan: GraphPlan) -> torch.Tensor:
     """The plan's column order: int32 [num_cols], position -> column of the backward's column
     blocks (the identity for plans without one)."""
