@@ -32,6 +32,7 @@ from .ops import (  # noqa: F401
     spgemm_backward,
     spgemm_edge_grad,
     spgemm_forward,
+    subgraph_row_limits,
 )
 from .autograd import (  # noqa: F401
     CSRGraph,
@@ -78,6 +79,12 @@ from .sampling import (  # noqa: F401,E402
     sample_neighbors,
     to_block,
 )
+from .subgraph import (  # noqa: F401,E402
+    ClusterLoader,
+    Subgraph,
+    node_subgraph,
+    random_partition,
+)
 from .layers import (  # noqa: F401,E402
     MaxKGCN,
     MaxKGATConv,
@@ -103,6 +110,7 @@ __all__ = [
     "max_row_limits",
     "sample_neighbors", "block_compact", "Block", "to_block", "NeighborSampler", "layer_seed",
     "block_aggregate", "block_self_aggregate", "block_spgemm", "sample_row_limits",
+    "node_subgraph", "Subgraph", "random_partition", "ClusterLoader", "subgraph_row_limits",
 ]
 
 ABI_VERSION = lib.maxk_abi_version()

@@ -116,6 +116,12 @@ SIGNATURES = {
     "maxk_block_compact_scratch_bytes": (ctypes.c_int64, [_i32]),
     "maxk_block_compact": (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i64,
                                           _i32, _vp]),
+    "maxk_induced_subgraph_scratch_bytes": (ctypes.c_int64, [_i32, _i32]),
+    "maxk_induced_subgraph_count": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64,
+                                                   _i32, _vp]),
+    "maxk_induced_subgraph_fill": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64,
+                                                  _i32, _i64, _i32, _vp]),
+    "maxk_subgraph_row_limits": (ctypes.c_int, [_vp, _i32]),
     "maxk_dense_spmm_csr": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "maxk_warp4_build": (ctypes.c_int, [_vp, _i32, _i32, _vp, _i64, ctypes.POINTER(_i64)]),
 }

@@ -1237,6 +1237,78 @@ def sample_row_limits() -> Tuple[int, ...]:
     return tuple(int(v) for v in buf)
 
 
+# -------------------------------------------------------------------------------------
+# Induced subgraphs (include/maxk_hip.h, "Induced subgraphs")
+# -------------------------------------------------------------------------------------
+def induced_subgraph_scratch_bytes(num_nodes: int, num_sel: int) -> int:
+    return int(lib.maxk_induced_subgraph_scratch_bytes(int(num_nodes), int(num_sel)))
+
+
+def _subgraph_args(ptr, idx, nodes):
+    _check_tensor(ptr, "ptr", torch.int32)
+    _need(ptr.dim() == 1 and ptr.numel() >= 1, "ptr must have num_nodes+1 entries")
+    dev = ptr.device
+    _vector(idx, "idx", torch.int32, None, "num_edges", dev)
+    _vector(nodes, "nodes", torch.int32, None, "num_sel", dev)
+    return ptr.numel() - 1, idx.numel(), nodes.numel(), dev
+
+
+def induced_subgraph_count(ptr, idx, nodes, out=None, scratch=None):
+    """``(out_ptr int32 [S + 1], counts int32 [3])`` of ``A[nodes][:, nodes]``: the exclusive
+    scan of the kept edges per position of ``nodes``, and ``{M, distinct nodes, entries out of
+    range}`` on the device (``maxk_induced_subgraph_count``). Nothing is read back here. ``out``:
+    the two buffers, pre-allocated; ``scratch``: a u8 buffer of
+    :func:`induced_subgraph_scratch_bytes` bytes. With both given the call allocates nothing and
+    can be captured into a graph."""
+    n, e, s, dev = _subgraph_args(ptr, idx, nodes)
+    if out is None:
+        out = (torch.empty(s + 1, dtype=torch.int32, device=dev),
+               torch.empty(3, dtype=torch.int32, device=dev))
+    out_ptr, counts = out
+    _vector(out_ptr, "out_ptr", torch.int32, s + 1, "num_sel + 1", dev)
+    _vector(counts, "counts", torch.int32, 3, "3", dev)
+    scratch = _scratch(scratch, induced_subgraph_scratch_bytes(n, s), dev)
+    with _device(dev):
+        check(lib.maxk_induced_subgraph_count(_p(ptr), _p(idx), _p(nodes), _p(out_ptr),
+                                              _p(counts), _p(scratch), scratch.numel(), n, e, s,
+                                              _stream()), "induced_subgraph_count")
+    return out_ptr, counts
+
+
+def induced_subgraph_fill(ptr, idx, nodes, out_ptr, capacity: Optional[int] = None, out=None,
+                          scratch=None):
+    """``(out_col int32 [capacity], out_eid int32 [capacity])``: the local column and the edge
+    number in the parent of every kept edge, behind the ``out_ptr`` of
+    :func:`induced_subgraph_count` on the same inputs (``maxk_induced_subgraph_fill``). Entries at
+    and past ``out_ptr[S]`` are not written, and nothing is read back here. ``out``: the two
+    buffers, pre-allocated (``capacity = out[0].numel()``); ``scratch`` as for the count."""
+    n, e, s, dev = _subgraph_args(ptr, idx, nodes)
+    _vector(out_ptr, "out_ptr", torch.int32, s + 1, "num_sel + 1", dev)
+    if out is None:
+        _need(capacity is not None and int(capacity) >= 0, "capacity or out must be given")
+        out = (torch.empty(int(capacity), dtype=torch.int32, device=dev),
+               torch.empty(int(capacity), dtype=torch.int32, device=dev))
+    out_col, out_eid = out
+    _vector(out_col, "out_col", torch.int32, None, "capacity", dev)
+    _vector(out_eid, "out_eid", torch.int32, out_col.numel(), "capacity", dev)
+    scratch = _scratch(scratch, induced_subgraph_scratch_bytes(n, s), dev)
+    with _device(dev):
+        check(lib.maxk_induced_subgraph_fill(_p(ptr), _p(idx), _p(nodes), _p(out_ptr),
+                                             _p(out_col), _p(out_eid), out_col.numel(),
+                                             _p(scratch), scratch.numel(), n, e, s, _stream()),
+              "induced_subgraph_fill")
+    return out_col, out_eid
+
+
+def subgraph_row_limits() -> Tuple[int, ...]:
+    """``(short, medium)``: the row lengths at which the extraction switches regime
+    (``maxk_subgraph_row_limits``); exactly a limit's length runs in the regime below it."""
+    count = lib.maxk_subgraph_row_limits(None, 0)
+    buf = (ctypes.c_int32 * count)()
+    lib.maxk_subgraph_row_limits(ctypes.cast(buf, ctypes.c_void_p), count)
+    return tuple(int(v) for v in buf)
+
+
 def plan_col_order(plan: GraphPlan) -> torch.Tensor:
     """The plan's column order: int32 [num_cols], position -> column of the backward's column
     blocks (the identity for plans without one)."""
