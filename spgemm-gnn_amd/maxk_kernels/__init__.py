@@ -18,6 +18,7 @@ from .ops import (  # noqa: F401
     TOPK_MODES,
     GraphPlan,
     cbsr_stats,
+    csr_transpose,
     clear_plan_cache,
     dense_spmm,
     edge_softmax_backward,
@@ -33,6 +34,7 @@ from .ops import (  # noqa: F401
     spgemm_edge_grad,
     spgemm_forward,
     subgraph_row_limits,
+    transpose_digit_bits,
 )
 from .autograd import (  # noqa: F401
     CSRGraph,
@@ -111,6 +113,7 @@ __all__ = [
     "sample_neighbors", "block_compact", "Block", "to_block", "NeighborSampler", "layer_seed",
     "block_aggregate", "block_self_aggregate", "block_spgemm", "sample_row_limits",
     "node_subgraph", "Subgraph", "random_partition", "ClusterLoader", "subgraph_row_limits",
+    "csr_transpose", "transpose_digit_bits",
 ]
 
 ABI_VERSION = lib.maxk_abi_version()

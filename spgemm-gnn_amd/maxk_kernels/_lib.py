@@ -122,6 +122,10 @@ SIGNATURES = {
     "maxk_induced_subgraph_fill": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64,
                                                   _i32, _i64, _i32, _vp]),
     "maxk_subgraph_row_limits": (ctypes.c_int, [_vp, _i32]),
+    "maxk_csr_transpose_scratch_bytes": (ctypes.c_int64, [_i32, _i32, _i64]),
+    "maxk_csr_transpose": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32,
+                                          _i64, _vp]),
+    "maxk_transpose_digit_bits": (ctypes.c_int, [_i32, _vp, _i32]),
     "maxk_dense_spmm_csr": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "maxk_warp4_build": (ctypes.c_int, [_vp, _i32, _i32, _vp, _i64, ctypes.POINTER(_i64)]),
 }

@@ -79,6 +79,23 @@ def _check_values_version(ctx) -> None:
             "graph.val, or pass the changing values as edge_weight=")
 
 
+def _torch_transpose(ptr, idx, num_cols: int, rows=None):
+    """``(ptr_t int64 [num_cols + 1], rows int64 [E], order int64 [E])``: the transposition in
+    torch, a stable argsort of the int64 key ``column * num_rows + row``. The path of CPU tensors;
+    on the GPU ``ops.csr_transpose`` computes the same (tests/test_gpu_transpose.py,
+    tools/transpose_time.py). ``rows``: the row of every edge, when the caller has it."""
+    n = ptr.numel() - 1
+    if rows is None:
+        rows = torch.repeat_interleave(torch.arange(n, device=ptr.device),
+                                       (ptr[1:] - ptr[:-1]).to(torch.int64),
+                                       output_size=idx.numel())
+    cols = idx.to(torch.int64)
+    order = torch.argsort(cols * max(n, 1) + rows, stable=True)
+    ptr_t = torch.zeros(num_cols + 1, dtype=torch.int64, device=ptr.device)
+    ptr_t[1:] = torch.cumsum(torch.bincount(cols, minlength=num_cols), 0)
+    return ptr_t, rows, order
+
+
 @dataclass
 class CSRGraph:
     """Destination-row CSR adjacency: row r aggregates from columns idx[ptr[r]:ptr[r+1]].
@@ -162,7 +179,10 @@ class CSRGraph:
         return (self.ptr[1:] - self.ptr[:-1]).to(torch.int64)
 
     def out_degrees(self) -> torch.Tensor:
-        return torch.bincount(self.idx.to(torch.int64), minlength=self.num_nodes)
+        st = self._values.get("transposed_structure")
+        if st is not None:      # the column counts are the row lengths of A^T
+            return (st[0][1:] - st[0][:-1]).to(torch.int64)
+        return torch.bincount(self.idx.to(torch.int64), minlength=self._num_cols())
 
     def edge_rows(self) -> torch.Tensor:
         """The destination row of every edge, int64 ``[E]`` in CSR edge order (cached): the
@@ -206,20 +226,40 @@ class CSRGraph:
         self._values[kind] = v
         return v
 
+    # -- A^T ---------------------------------------------------------------------------
+    def _num_cols(self) -> int:
+        return self.num_nodes
+
+    def _transposed_graph(self, ptr_t, idx_t, val_t) -> "CSRGraph":
+        return CSRGraph(ptr_t, idx_t, val_t)
+
+    def _transpose(self, with_val: bool = False):
+        """``(ptr_t, idx_t, order[, val_t])`` of A^T. On the GPU the HIP transposition
+        (``ops.csr_transpose``): all int32, ``order`` included, and ``val_t`` the kernel's gather.
+        On CPU tensors :func:`_torch_transpose`: ``ptr_t`` and ``order`` int64."""
+        if self.ptr.is_cuda:
+            return ops.csr_transpose(self.ptr, self.idx, self.val if with_val else None,
+                                     self._num_cols())
+        ptr_t, rows, order = _torch_transpose(self.ptr, self.idx, self._num_cols(),
+                                              self._values.get("edge_rows"))
+        idx_t = rows[order].to(torch.int32).contiguous()
+        return (ptr_t, idx_t, order) + ((self.val[order],) if with_val else ())
+
     def transposed(self) -> "CSRGraph":
         """A^T with the same edge values (row = source node), cached: the backward of the
         dense aggregation, dX = A^T dY, runs the same SpMM kernel on it."""
         key = ("transposed", self.val.data_ptr(), ops._version(self.val))
         g = self._values.get(key)
         if g is None:
-            rows = torch.repeat_interleave(torch.arange(self.num_nodes, device=self.device),
-                                           self.in_degrees())
-            cols = self.idx.to(torch.int64)
-            order = torch.argsort(cols * self.num_nodes + rows, stable=True)
-            cnt = torch.bincount(cols, minlength=self.num_nodes)
-            ptr = torch.zeros(self.num_nodes + 1, dtype=torch.int64, device=self.device)
-            ptr[1:] = torch.cumsum(cnt, 0)
-            g = CSRGraph(ptr, rows[order], self.val[order])
+            st = self._values.get("transposed_structure")
+            if st is not None:      # sorted already: the values are gathered
+                ptr_t, idx_t, val_t = st[0], st[1], self.val[st[2]]
+            elif self.val.requires_grad:    # the gather stays differentiable in val
+                ptr_t, idx_t, order = self._transpose()
+                val_t = self.val[order.to(torch.int64)]
+            else:
+                ptr_t, idx_t, _, val_t = self._transpose(with_val=True)
+            g = self._transposed_graph(ptr_t, idx_t, val_t)
             self._values = {k: v for k, v in self._values.items()
                             if not (isinstance(k, tuple) and k[0] == "transposed")}
             self._values[key] = g
@@ -230,13 +270,10 @@ class CSRGraph:
         so changing values are transposed by one gather and no sort."""
         st = self._values.get("transposed_structure")
         if st is None:
-            rows = torch.repeat_interleave(torch.arange(self.num_nodes, device=self.device),
-                                           self.in_degrees())
-            cols = self.idx.to(torch.int64)
-            order = torch.argsort(cols * self.num_nodes + rows, stable=True)
-            ptr = torch.zeros(self.num_nodes + 1, dtype=torch.int64, device=self.device)
-            ptr[1:] = torch.cumsum(torch.bincount(cols, minlength=self.num_nodes), 0)
-            st = (ptr.to(torch.int32), rows[order].to(torch.int32).contiguous(), order)
+            ptr_t, idx_t, order = self._transpose()
+            if order.dtype == torch.int32:      # the kernel's: kept as transposed_order()
+                self._values.setdefault("transposed_order", order)
+            st = (ptr_t.to(torch.int32), idx_t, order.to(torch.int64))
             self._values["transposed_structure"] = st
         return st
 
@@ -246,7 +283,7 @@ class CSRGraph:
         order = self._values.get("transposed_order")
         if order is None:
             order = self.transposed_structure()[2].to(torch.int32).contiguous()
-            self._values["transposed_order"] = order
+            order = self._values.setdefault("transposed_order", order)
         return order
 
     def with_values(self, kind: str) -> "CSRGraph":

@@ -1309,6 +1309,62 @@ def subgraph_row_limits() -> Tuple[int, ...]:
     return tuple(int(v) for v in buf)
 
 
+# -------------------------------------------------------------------------------------
+# CSR transposition (include/maxk_hip.h, "CSR transposition")
+# -------------------------------------------------------------------------------------
+def csr_transpose_scratch_bytes(num_rows: int, num_cols: int, num_edges: int) -> int:
+    return int(lib.maxk_csr_transpose_scratch_bytes(int(num_rows), int(num_cols),
+                                                    int(num_edges)))
+
+
+def transpose_digit_bits(num_cols: int) -> Tuple[int, ...]:
+    """The digit widths, lowest digit first, of the radix passes :func:`csr_transpose` runs for
+    ``num_cols`` columns (``maxk_transpose_digit_bits``)."""
+    count = lib.maxk_transpose_digit_bits(int(num_cols), None, 0)
+    buf = (ctypes.c_int32 * count)()
+    lib.maxk_transpose_digit_bits(int(num_cols), ctypes.cast(buf, ctypes.c_void_p), count)
+    return tuple(int(v) for v in buf)
+
+
+def csr_transpose(ptr, idx, val=None, num_cols: Optional[int] = None, out=None, scratch=None):
+    """``(ptr_t int32 [num_cols + 1], idx_t int32 [E], order int32 [E][, val_t f32 [E]])``: A^T of
+    the CSR graph ``(ptr, idx)`` of ``num_cols`` columns (default: square), by the rule of the
+    header (``maxk_csr_transpose``): edge ``j`` of A^T is edge ``order[j]`` of A, the edges of a
+    column in ascending edge number, ``idx_t`` their rows, ``val_t = val[order]`` bit for bit
+    (returned when ``val`` is given). ``out``: the three or four buffers, pre-allocated;
+    ``scratch``: a u8 buffer of :func:`csr_transpose_scratch_bytes` bytes. With both given the
+    call allocates nothing and can be captured into a graph."""
+    _check_tensor(ptr, "ptr", torch.int32)
+    _need(ptr.dim() == 1 and ptr.numel() >= 1, "ptr must have num_rows+1 entries")
+    dev = ptr.device
+    _vector(idx, "idx", torch.int32, None, "num_edges", dev)
+    n, e = ptr.numel() - 1, idx.numel()
+    nc = n if num_cols is None else int(num_cols)
+    _need(nc >= 0, "num_cols must not be negative")
+    if val is not None:
+        _vector(val, "val", torch.float32, e, "num_edges", dev)
+    if out is None:
+        out = (torch.empty(nc + 1, dtype=torch.int32, device=dev),
+               torch.empty(e, dtype=torch.int32, device=dev),
+               torch.empty(e, dtype=torch.int32, device=dev))
+        if val is not None:
+            out += (torch.empty(e, dtype=torch.float32, device=dev),)
+    _need(len(out) == (3 if val is None else 4),
+          "out must hold ptr_t, idx_t, order, and val_t exactly when val is given")
+    _vector(out[0], "ptr_t", torch.int32, nc + 1, "num_cols + 1", dev)
+    _vector(out[1], "idx_t", torch.int32, e, "num_edges", dev)
+    _vector(out[2], "order", torch.int32, e, "num_edges", dev)
+    if val is not None:
+        _vector(out[3], "val_t", torch.float32, e, "num_edges", dev)
+    scratch = _scratch(scratch, csr_transpose_scratch_bytes(n, nc, e), dev)
+    with _device(dev):
+        check(lib.maxk_csr_transpose(_p(ptr), _p(idx), _p(val), _p(out[0]), _p(out[1]),
+                                     _p(out[2]), _p(out[3] if val is not None else None),
+                                     _p(scratch), scratch.numel(), n, nc, e, _stream()),
+              "csr_transpose")
+    return tuple(out)
+
+
 def plan_col_order(plan: GraphPlan) -> torch.Tensor:
     """The plan's column order: int32 [num_cols], position -> column of the backward's column
     blocks (the identity for plans without one)."""

@@ -15,7 +15,7 @@
   (``HeadsAggregateFunction`` with ``alpha = block.val[None]``). A block lives for one step, where
   a plan's sorts would never pay back. ``D % 4 == 0`` and ``k <= D <= 256`` (that kernel's limit).
 
-The backward needs the block's transposed structure, which stays a torch sort per block.
+The backward needs the block's transposed structure: ``ops.csr_transpose`` per block.
 """
 from __future__ import annotations
 
@@ -96,36 +96,19 @@ class Block(CSRGraph):
         raise NotImplementedError("edge_weight on a Block is not implemented: block_aggregate "
                                   "and block_self_aggregate take the block's own values")
 
-    def out_degrees(self) -> torch.Tensor:
-        return torch.bincount(self.idx.to(torch.int64), minlength=self.num_src)
+    def _num_cols(self) -> int:
+        return self.num_src
+
+    def _transposed_graph(self, ptr_t, idx_t, val_t) -> "Block":
+        """A^T, ``num_src`` rows over ``num_dst`` columns."""
+        return Block(ptr_t, idx_t, val_t, num_src=self.num_dst)
 
     def _transpose_order(self):
-        rows = self.edge_rows()
-        cols = self.idx.to(torch.int64)
-        order = torch.argsort(cols * max(self.num_dst, 1) + rows, stable=True)
-        ptr = torch.zeros(self.num_src + 1, dtype=torch.int64, device=self.device)
-        ptr[1:] = torch.cumsum(torch.bincount(cols, minlength=self.num_src), 0)
-        return ptr, rows, order
-
-    def transposed(self) -> "Block":
-        """A^T, ``num_src`` rows over ``num_dst`` columns, with the same edge values (cached)."""
-        key = ("transposed", self.val.data_ptr(), ops._version(self.val))
-        g = self._values.get(key)
-        if g is None:
-            ptr, rows, order = self._transpose_order()
-            g = Block(ptr, rows[order], self.val[order], num_src=self.num_dst)
-            self._values = {k: v for k, v in self._values.items()
-                            if not (isinstance(k, tuple) and k[0] == "transposed")}
-            self._values[key] = g
-        return g
-
-    def transposed_structure(self):
-        st = self._values.get("transposed_structure")
-        if st is None:
-            ptr, rows, order = self._transpose_order()
-            st = (ptr.to(torch.int32), rows[order].to(torch.int32).contiguous(), order)
-            self._values["transposed_structure"] = st
-        return st
+        """``(ptr_t, idx_t, order)`` of A^T over ``num_src`` columns: ``CSRGraph._transpose``, the
+        HIP transposition on the GPU and the torch sort on CPU tensors. ``out_degrees``,
+        ``transposed``, ``transposed_structure`` and ``transposed_order`` are the inherited ones
+        on top of it."""
+        return self._transpose()
 
     def with_values(self, kind: str) -> "Block":
         key = ("graph", kind)

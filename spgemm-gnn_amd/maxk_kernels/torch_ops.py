@@ -31,6 +31,11 @@ formula (the SSpMM backward) as a registered derivative.
                                   -> [N, D]   (MaxK that also emits the dense masked row; the
                                      scatter adds the dense row's gradient; p = 0: no dropout)
 
+    torch.ops.maxk.csr_transpose(ptr, idx, val (or None), num_cols)
+                                  -> (ptr_t [num_cols + 1], idx_t [E], order [E], val_t [E], all
+                                     int32 but the f32 val_t, which is empty without val): A^T of a
+                                     CSR graph; shapes from the inputs' shapes, no derivative
+
 The real kernels are :mod:`maxk_kernels.ops` (the HIP C ABI); there is no other
 implementation behind these names. Differences from the plain functions, all forced by
 the operator schema: ``maxk_forward`` always returns the selectors (the reference drops
@@ -298,3 +303,22 @@ def _maxk_dense_backward(ctx, grad_dense, grad_data, grad_index):
 
 
 maxk_dense_forward.register_autograd(_maxk_dense_backward, setup_context=_maxk_dense_setup)
+
+
+# A^T of a CSR graph (ops.csr_transpose). The output shapes follow from the input shapes and
+# num_cols alone, so it has a fake kernel; structure has no derivative.
+@torch.library.custom_op(f"{_NS}::csr_transpose", mutates_args=())
+def csr_transpose(ptr: torch.Tensor, idx: torch.Tensor, val: Optional[torch.Tensor],
+                  num_cols: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``(ptr_t, idx_t, order, val_t)``; ``val_t`` has no elements when ``val`` is ``None``."""
+    out = ops.csr_transpose(ptr, idx, val, num_cols)
+    if val is None:
+        out += (torch.empty(0, dtype=torch.float32, device=ptr.device),)
+    return out
+
+
+@csr_transpose.register_fake
+def _(ptr, idx, val, num_cols):
+    e = idx.shape[0]
+    return (idx.new_empty((num_cols + 1,)), idx.new_empty((e,)), idx.new_empty((e,)),
+            idx.new_empty((e if val is not None else 0,), dtype=torch.float32))

@@ -7,12 +7,21 @@
 // words on a shape without them) and that every table entry is selected by some input, so no
 // instantiation is dead. It prints the tables' kernel names, sorted, one per line, as
 // tests/golden/kernel_instantiations.txt lists them; problems go to stderr and exit status 1.
+//
+//   variant_check transpose
+//
+// does the same for the tables of csrc/variants_transpose.h alone (the transposition's passes over
+// every pass count, and its digit plan over every key width); their names are the pass kernels of
+// tests/golden/kernel_instantiations_transpose.txt.
 #include <algorithm>
+#include <climits>
 #include <cstdio>
+#include <cstring>
 #include <string>
 #include <vector>
 
 #include "variants.h"
+#include "variants_transpose.h"
 
 using namespace maxk;
 
@@ -57,7 +66,49 @@ struct Family {
   }
 };
 
-int main() {
+static int finish() {
+  std::sort(g_names.begin(), g_names.end());
+  for (const std::string& n : g_names) std::puts(n.c_str());
+  return g_bad;
+}
+
+// The tables of variants_transpose.h: every pass of every pass count, with and without values;
+// and the digit plan of every key width: widths within the limit that sum to the key's bits.
+static int check_transpose() {
+  using namespace maxk_tr;
+  const bool tf[] = {false, true};
+  {
+    Family pass("tr_pass", kPassVariants);
+    Family hist("tr_hist", kHistVariants);
+    for (int passes = 1; passes <= kTrMaxPasses; ++passes)
+      for (int p = 0; p < passes; ++p) {
+        for (bool val : tf) pass.selected(select_pass_variant(p, passes, val));
+        hist.selected(select_hist_variant(p));
+      }
+  }
+  for (int b = 0; b <= 31; ++b)
+    for (long long nc : {(1ll << b) - 1, 1ll << b, (1ll << b) + 1}) {
+      if (nc > INT32_MAX) continue;
+      const int32_t n = (int32_t)nc;
+      const int passes = pass_count(n);
+      int sum = 0, widest = 0;
+      bool ok = passes >= 1 && passes <= kTrMaxPasses;
+      for (int p = 0; p < passes; ++p) {
+        const int w = digit_bits(n, p);
+        ok = ok && digit_shift(n, p) == sum;
+        sum += w;
+        widest = w > widest ? w : widest;
+      }
+      if (!ok || sum != key_bits(n) || widest > kTrMaxDigitBits || (1ll << sum) < nc) {
+        std::fprintf(stderr, "transpose: bad digit plan for %lld columns\n", nc);
+        g_bad = 1;
+      }
+    }
+  return finish();
+}
+
+int main(int argc, char** argv) {
+  if (argc > 1 && std::strcmp(argv[1], "transpose") == 0) return check_transpose();
   const bool tf[] = {false, true};
   {
     Family fam("forward", kFwdVariants);
@@ -136,7 +187,5 @@ int main() {
     Family fam("dense_spmm", kDenseSpmmVariants);
     for (int d = 4; d <= 1024; d += 4) fam.selected(select_dense_spmm_variant(d));
   }
-  std::sort(g_names.begin(), g_names.end());
-  for (const std::string& n : g_names) std::puts(n.c_str());
-  return g_bad;
+  return finish();
 }
