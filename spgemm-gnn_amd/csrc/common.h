@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -114,6 +115,64 @@ int dispatch_variant(const Table& table, const V& v, Fn&& fn) {
 inline bool ranges_overlap(const void* a, int64_t na, const void* b, int64_t nb) {
   const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
   return na > 0 && nb > 0 && x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
+}
+
+// An array argument of an entry point; an optional one that is absent has no bytes.
+struct Range {
+  const void* p;
+  int64_t bytes;
+};
+
+// Refuses a null pointer with bytes, and an output that shares a byte with an input or with
+// another output. w: the entry point's name and ": ".
+inline int check_ranges(const std::string& w, const Range* ins, int nin, const Range* outs,
+                        int nout) {
+  bool null = false;
+  for (int i = 0; i < nin; ++i) null = null || (ins[i].bytes > 0 && !ins[i].p);
+  for (int i = 0; i < nout; ++i) null = null || (outs[i].bytes > 0 && !outs[i].p);
+  MAXK_CHECK_ARG(!null, w + "null pointer");
+  bool overlap = false;
+  for (int o = 0; o < nout; ++o) {
+    for (int i = 0; i < nin; ++i)
+      overlap = overlap || ranges_overlap(outs[o].p, outs[o].bytes, ins[i].p, ins[i].bytes);
+    for (int i = o + 1; i < nout; ++i)
+      overlap = overlap || ranges_overlap(outs[o].p, outs[o].bytes, outs[i].p, outs[i].bytes);
+  }
+  MAXK_CHECK_ARG(!overlap, w + "an output overlaps an input or another output");
+  return MAXK_OK;
+}
+
+// The body of a maxk_*_row_limits export: the first min(count, capacity) limits into out (NULL:
+// none), and the count.
+inline int copy_limits(int32_t* out, int32_t capacity, std::initializer_list<int32_t> limits) {
+  int i = 0;
+  for (int32_t v : limits) {
+    if (out && i < capacity) out[i] = v;
+    ++i;
+  }
+  return i;
+}
+
+__device__ __forceinline__ int32_t clampi(int32_t c, int32_t hi) {
+  return c < 0 ? 0 : (c > hi ? hi : c);
+}
+
+// Segment [lo, hi) of the row that entry i of row_ids names (empty for i >= count); ptr is
+// clamped into [0, E] and the row into [0, num_rows): memory safety whatever the arrays hold.
+__device__ __forceinline__ void clamped_segment(const int32_t* __restrict__ ptr,
+                                                const int32_t* __restrict__ row_ids, int64_t i,
+                                                int32_t count, int32_t num_rows, int64_t E,
+                                                int64_t& lo, int64_t& hi) {
+  lo = 0;
+  hi = 0;
+  if (i < count) {
+    const int32_t r = clampi(row_ids[i], num_rows - 1);
+    int64_t b = ptr[r], e = ptr[r + 1];
+    b = b < 0 ? 0 : (b > E ? E : b);
+    e = e < b ? b : (e > E ? E : e);
+    lo = b;
+    hi = e;
+  }
 }
 
 // Forward work item: a run of whole destination rows [row0, row0+nrows) (or, nrows < 0, one

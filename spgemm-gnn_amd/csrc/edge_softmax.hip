@@ -151,7 +151,5 @@ extern "C" int maxk_edge_softmax_backward(const int32_t* ptr, const float* y, co
 }
 
 extern "C" int maxk_edge_softmax_row_limits(int32_t* out, int32_t capacity) {
-  const int32_t limits[2] = {maxk::kEsShortMax, maxk::kEsMediumMax};
-  for (int i = 0; i < 2 && out && i < capacity; ++i) out[i] = limits[i];
-  return 2;
+  return maxk::copy_limits(out, capacity, {maxk::kEsShortMax, maxk::kEsMediumMax});
 }

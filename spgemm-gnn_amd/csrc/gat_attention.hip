@@ -31,10 +31,6 @@
 
 namespace maxk {
 
-__device__ __forceinline__ int32_t gat_clamp(int32_t c, int32_t hi) {
-  return c < 0 ? 0 : (c > hi ? hi : c);
-}
-
 // Element j of a row's scores: idx at the row's segment, el [num_cols], er_r the row's own score.
 // idx is clamped into [0, num_cols) before use, as es_segment clamps ptr.
 struct GatScore {
@@ -43,7 +39,7 @@ struct GatScore {
   float er_r, slope;
   int32_t col_hi;
   __device__ __forceinline__ float z(int32_t j) const {
-    return el[gat_clamp(idx[j], col_hi)] + er_r;
+    return el[clampi(idx[j], col_hi)] + er_r;
   }
   __device__ __forceinline__ float operator()(int32_t j) const {
     const float v = z(j);
@@ -62,7 +58,7 @@ struct GatPermuted {
   const float* __restrict__ values;
   int32_t edge_hi;
   __device__ __forceinline__ float operator()(int32_t j) const {
-    return values[gat_clamp(order[j], edge_hi)];
+    return values[clampi(order[j], edge_hi)];
   }
 };
 
@@ -148,29 +144,6 @@ __global__ __launch_bounds__(kEsThreads) void edge_colsum_heads_kernel(
 namespace maxk {
 
 // ------------------------------------------------------------------------------ entry points
-struct GatRange {
-  const void* p;
-  int64_t bytes;
-};
-
-// null pointers with edges, and an output that shares a byte with an input or another output
-static int gat_check_ranges(const std::string& w, const GatRange* ins, int nin,
-                            const GatRange* outs, int nout) {
-  bool null = false;
-  for (int i = 0; i < nin; ++i) null = null || (ins[i].bytes > 0 && !ins[i].p);
-  for (int i = 0; i < nout; ++i) null = null || (outs[i].bytes > 0 && !outs[i].p);
-  MAXK_CHECK_ARG(!null, w + "null pointer");
-  bool overlap = false;
-  for (int o = 0; o < nout; ++o) {
-    for (int i = 0; i < nin; ++i)
-      overlap = overlap || ranges_overlap(outs[o].p, outs[o].bytes, ins[i].p, ins[i].bytes);
-    for (int i = o + 1; i < nout; ++i)
-      overlap = overlap || ranges_overlap(outs[o].p, outs[o].bytes, outs[i].p, outs[i].bytes);
-  }
-  MAXK_CHECK_ARG(!overlap, w + "an output overlaps an input or another output");
-  return MAXK_OK;
-}
-
 static int gat_check_sizes(const std::string& w, int32_t num_rows, int32_t num_cols, int64_t E) {
   MAXK_CHECK_ARG(num_rows >= 0 && num_cols >= 0 && E >= 0 && E <= (int64_t)INT32_MAX,
                  w + "sizes out of range");
@@ -207,10 +180,10 @@ static int gat_forward_impl(const std::string& w, const int32_t* ptr, const int3
   if (num_edges == 0 || num_rows == 0) return MAXK_OK;
   MAXK_CHECK_ARG(num_cols > 0, w + "sizes out of range: edges without columns");
   const int64_t E = num_edges;
-  const GatRange ins[4] = {{ptr, 4 * ((int64_t)num_rows + 1)}, {idx, 4 * E},
+  const Range ins[4] = {{ptr, 4 * ((int64_t)num_rows + 1)}, {idx, 4 * E},
                            {el, 4 * H * (int64_t)num_cols}, {er, 4 * H * (int64_t)num_rows}};
-  const GatRange outs[1] = {{alpha, 4 * H * E}};
-  rc = gat_check_ranges(w, ins, 4, outs, 1);
+  const Range outs[1] = {{alpha, 4 * H * E}};
+  rc = check_ranges(w, ins, 4, outs, 1);
   if (rc != MAXK_OK) return rc;
   if (heads)
     hipLaunchKernelGGL(maxk_mh::gat_attention_fwd_heads_kernel, gat_grid(num_rows, H),
@@ -243,11 +216,11 @@ static int gat_backward_impl(const std::string& w, const int32_t* ptr, const int
     return MAXK_OK;
   }
   MAXK_CHECK_ARG(num_cols > 0, w + "sizes out of range: edges without columns");
-  const GatRange ins[6] = {{ptr, 4 * ((int64_t)num_rows + 1)}, {idx, 4 * E},
+  const Range ins[6] = {{ptr, 4 * ((int64_t)num_rows + 1)}, {idx, 4 * E},
                            {el, 4 * H * (int64_t)num_cols}, {er, 4 * H * (int64_t)num_rows},
                            {alpha, 4 * H * E}, {grad_alpha, 4 * H * E}};
-  const GatRange outs[2] = {{grad_edge, 4 * H * E}, {grad_er, 4 * H * (int64_t)num_rows}};
-  rc = gat_check_ranges(w, ins, 6, outs, 2);
+  const Range outs[2] = {{grad_edge, 4 * H * E}, {grad_er, 4 * H * (int64_t)num_rows}};
+  rc = check_ranges(w, ins, 6, outs, 2);
   if (rc != MAXK_OK) return rc;
   if (heads)
     hipLaunchKernelGGL(maxk_mh::gat_attention_bwd_heads_kernel, gat_grid(num_rows, H),
@@ -275,10 +248,10 @@ static int gat_colsum_impl(const std::string& w, const int32_t* ptr_t, const int
     MAXK_HIP_TRY(hipMemsetAsync(out, 0, 4 * (size_t)H * (size_t)num_cols, (hipStream_t)stream));
     return MAXK_OK;
   }
-  const GatRange ins[3] = {{ptr_t, 4 * ((int64_t)num_cols + 1)}, {order, 4 * E},
+  const Range ins[3] = {{ptr_t, 4 * ((int64_t)num_cols + 1)}, {order, 4 * E},
                            {values, 4 * H * E}};
-  const GatRange outs[1] = {{out, 4 * H * (int64_t)num_cols}};
-  rc = gat_check_ranges(w, ins, 3, outs, 1);
+  const Range outs[1] = {{out, 4 * H * (int64_t)num_cols}};
+  rc = check_ranges(w, ins, 3, outs, 1);
   if (rc != MAXK_OK) return rc;
   if (heads)
     hipLaunchKernelGGL(maxk_mh::edge_colsum_heads_kernel, gat_grid(num_cols, H), dim3(kEsThreads),

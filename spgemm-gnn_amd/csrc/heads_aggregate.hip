@@ -29,12 +29,10 @@
 
 namespace maxk_mh {
 
-using maxk::ranges_overlap;
+using maxk::check_ranges;
+using maxk::clampi;
+using maxk::Range;
 using maxk::set_error;
-
-__device__ __forceinline__ int32_t clampi(int32_t c, int32_t hi) {
-  return c < 0 ? 0 : (c > hi ? hi : c);
-}
 
 // Segment [b, b + n) of row `row` of ptr, clamped into [0, E]; n = 0 past num_rows.
 __device__ __forceinline__ void segment(const int32_t* __restrict__ ptr, int64_t row,
@@ -374,11 +372,6 @@ __global__ __launch_bounds__(kHeadsThreads) void heads_bwd_kernel(const BwdArgs 
 }
 
 // ------------------------------------------------------------------------------ entry points
-struct Range {
-  const void* p;
-  int64_t bytes;
-};
-
 // sizes, k, heads and strides shared by both calls; strides are resolved (0: the row width)
 static int check_shape(const std::string& w, int32_t H, int32_t num_rows, int32_t num_cols,
                        int64_t E, int32_t D, int32_t k, int64_t& ds, int64_t& is) {
@@ -401,22 +394,6 @@ static int check_shape(const std::string& w, int32_t H, int32_t num_rows, int32_
   MAXK_CHECK_ARG(is >= k, w + "index_stride must be >= k (0: k)");
   MAXK_CHECK_ARG(E == 0 || num_cols > 0, w + "sizes out of range: edges without columns");
   MAXK_CHECK_ARG(E == 0 || num_rows > 0, w + "sizes out of range: edges without rows");
-  return MAXK_OK;
-}
-
-static int check_ranges(const std::string& w, const Range* ins, int nin, const Range* outs,
-                        int nout) {
-  bool null = false;
-  for (int i = 0; i < nin; ++i) null = null || (ins[i].bytes > 0 && !ins[i].p);
-  MAXK_CHECK_ARG(!null, w + "null pointer");
-  bool overlap = false;
-  for (int o = 0; o < nout; ++o) {
-    for (int i = 0; i < nin; ++i)
-      overlap = overlap || ranges_overlap(outs[o].p, outs[o].bytes, ins[i].p, ins[i].bytes);
-    for (int i = o + 1; i < nout; ++i)
-      overlap = overlap || ranges_overlap(outs[o].p, outs[o].bytes, outs[i].p, outs[i].bytes);
-  }
-  MAXK_CHECK_ARG(!overlap, w + "an output overlaps an input or another output");
   return MAXK_OK;
 }
 
@@ -527,8 +504,6 @@ extern "C" int maxk_heads_aggregate_backward(
 }
 
 extern "C" int maxk_heads_row_limits(int32_t* out, int32_t capacity) {
-  const int32_t limits[4] = {maxk_mh::kHeadsShortMax, maxk_mh::kHeadsMediumMax,
-                             maxk_mh::kHeadsShortMax, maxk_mh::kHeadsMediumMax};
-  for (int i = 0; i < 4 && out && i < capacity; ++i) out[i] = limits[i];
-  return 4;
+  return maxk::copy_limits(out, capacity, {maxk_mh::kHeadsShortMax, maxk_mh::kHeadsMediumMax,
+                                            maxk_mh::kHeadsShortMax, maxk_mh::kHeadsMediumMax});
 }

@@ -19,22 +19,23 @@
 // the edge order. The position of an edge inside its row replaces the edge number in the rank's low word
 // (the same order), so the bisection walks 32 key bits and ceil(log2 n) position bits.
 //
-// Both entry points need exclusive sums (over the seeds, over the columns); they run as three
-// launches on tiles of kSpScanTile items (tile sums, one work-group over the tile sums, apply),
-// in a fixed order, through caller-supplied scratch whose size an entry point reports.
+// Both entry points need exclusive sums (over the seeds, over the columns): the shared scan of
+// scan.h, through caller-supplied scratch whose size an entry point reports. The sampler scans its
+// counts as they are; the compaction's tile sums count the new and the seed columns, and its own
+// kernel places the new columns behind the scanned sums.
 #include <climits>
 
 #include "common.h"
+#include "scan.h"
 #include "variants_sample.h"
 
 namespace maxk_sp {
 
-using maxk::ranges_overlap;
+using maxk::check_ranges;
+using maxk::clampi;
+using maxk::Range;
 using maxk::set_error;
-
-__device__ __forceinline__ int32_t clampi(int32_t c, int32_t hi) {
-  return c < 0 ? 0 : (c > hi ? hi : c);
-}
+using maxk_scan::block_exclusive;
 
 __device__ __forceinline__ uint32_t fmix32(uint32_t x) {  // murmur3 finaliser
   x ^= x >> 16;
@@ -50,22 +51,15 @@ __device__ __forceinline__ uint32_t edge_key(uint32_t lo, uint32_t hi, uint32_t 
   return fmix32(fmix32(e ^ lo) ^ fmix32(e * 0x9E3779B1u + hi));
 }
 
-// Segment [b, b + n) of the row that seed position i names; ptr is clamped into [0, E] and the
-// seed into [0, num_rows) (memory safety, not a defined result).
+// Segment [b, b + n) of the row that seed position i names, clamped (memory safety, not a
+// defined result).
 __device__ __forceinline__ void seed_segment(const int32_t* __restrict__ ptr,
                                              const int32_t* __restrict__ seeds, int64_t i,
                                              int32_t S, int32_t num_rows, int64_t E, int64_t& b,
                                              int32_t& n) {
-  b = 0;
-  n = 0;
-  if (i < S) {
-    const int32_t r = clampi(seeds[i], num_rows - 1);
-    int64_t lo = ptr[r], hi = ptr[r + 1];
-    lo = lo < 0 ? 0 : (lo > E ? E : lo);
-    hi = hi < lo ? lo : (hi > E ? E : hi);
-    b = lo;
-    n = (int32_t)(hi - lo);
-  }
+  int64_t e;
+  maxk::clamped_segment(ptr, seeds, i, S, num_rows, E, b, e);
+  n = (int32_t)(e - b);
 }
 
 struct SampleArgs {
@@ -81,7 +75,7 @@ struct SampleArgs {
   uint32_t lo, hi;
 };
 
-// ------------------------------------------------------------------------------------- scans
+// ------------------------------------------------------------------------------------ counts
 // counts of the sampler: out_ptr[i] = min(n_i, fanout) (n_i for fanout < 0), out_ptr[S] = 0
 __global__ __launch_bounds__(kSpThreads) void sample_count_kernel(const SampleArgs a) {
   const int64_t i = (int64_t)blockIdx.x * kSpThreads + threadIdx.x;
@@ -90,121 +84,6 @@ __global__ __launch_bounds__(kSpThreads) void sample_count_kernel(const SampleAr
   int32_t n;
   seed_segment(a.ptr, a.seeds, i, a.S, a.num_rows, a.E, b, n);
   a.out_ptr[i] = (a.fanout < 0 || n < a.fanout) ? n : a.fanout;
-}
-
-constexpr int32_t kNewColumn = INT_MAX - 1;  // a sampled column that is no seed
-constexpr int32_t kNoColumn = INT_MAX;       // a column the block does not hold
-
-// item i of a scan: the value itself (mode 0), or whether column i is a new one (mode 1)
-__device__ __forceinline__ int32_t scan_item(int32_t v, int mode) {
-  return mode == 0 ? v : (int32_t)(v == kNewColumn);
-}
-
-__device__ __forceinline__ int32_t wave_sum(int32_t v) {
-#pragma unroll
-  for (int m = 1; m < kSpWave; m <<= 1) v += __shfl_xor(v, m, kSpWave);
-  return v;
-}
-
-// sums[b] = the sum of tile b's items; mode 1 also seeds[b] = the tile's seed columns (v < new)
-__global__ __launch_bounds__(kSpThreads) void scan_tile_sums_kernel(const int32_t* v, int64_t n,
-                                                                    int mode, int32_t* sums,
-                                                                    int32_t* seed_sums) {
-  __shared__ int32_t red[2][kSpWaves];
-  const int tid = threadIdx.x;
-  const int64_t base = (int64_t)blockIdx.x * kSpScanTile;
-  int32_t s = 0, t = 0;
-  for (int q = 0; q < kSpScanItems; ++q) {
-    const int64_t i = base + (int64_t)q * kSpThreads + tid;
-    if (i < n) {
-      const int32_t x = v[i];
-      s += scan_item(x, mode);
-      t += (int32_t)(x < kNewColumn);
-    }
-  }
-  s = wave_sum(s);
-  t = wave_sum(t);
-  if ((tid & (kSpWave - 1)) == 0) {
-    red[0][tid / kSpWave] = s;
-    red[1][tid / kSpWave] = t;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    sums[blockIdx.x] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-    if (mode == 1) seed_sums[blockIdx.x] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-  }
-}
-
-// Exclusive scan of the calling work-group's 256 values: returns the sum of the values of the
-// threads below, and the total in `total`. red: kSpWaves + 1 words of LDS, free on entry.
-__device__ __forceinline__ int32_t block_exclusive(int32_t v, int32_t* red, int32_t& total) {
-  const int tid = threadIdx.x, lane = tid & (kSpWave - 1), wave = tid / kSpWave;
-  int32_t inc = v;
-#pragma unroll
-  for (int m = 1; m < kSpWave; m <<= 1) {
-    const int32_t o = __shfl_up(inc, m, kSpWave);
-    if (lane >= m) inc += o;
-  }
-  if (lane == kSpWave - 1) red[wave] = inc;
-  __syncthreads();
-  int32_t before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < kSpWaves; ++w) {
-    const int32_t x = red[w];
-    before += w < wave ? x : 0;
-    all += x;
-  }
-  total = all;
-  __syncthreads();  // red is free again
-  return before + inc - v;
-}
-
-// One work-group: sums[0 .. nb) becomes its exclusive scan, totals[0] the grand total; with
-// seed_sums, totals[1] their sum (mode 1: {new columns, seed columns}).
-__global__ __launch_bounds__(kSpThreads) void scan_partials_kernel(int32_t* sums,
-                                                                   const int32_t* seed_sums,
-                                                                   int64_t nb, int32_t* totals) {
-  __shared__ int32_t red[kSpWaves + 1];
-  const int tid = threadIdx.x;
-  int32_t carry = 0, seeds = 0;
-  for (int64_t i0 = 0; i0 < nb; i0 += kSpThreads) {
-    const int64_t i = i0 + tid;
-    const int32_t v = i < nb ? sums[i] : 0;
-    int32_t total;
-    const int32_t ex = block_exclusive(v, red, total);
-    if (i < nb) sums[i] = carry + ex;
-    carry += total;
-    if (seed_sums) {
-      int32_t st;
-      block_exclusive(i < nb ? seed_sums[i] : 0, red, st);
-      seeds += st;
-    }
-  }
-  if (tid == 0) {
-    totals[0] = carry;
-    if (seed_sums) totals[1] = seeds;
-  }
-}
-
-// v[0 .. n) becomes its exclusive scan, in place (mode 0): a thread owns kSpScanItems
-// consecutive items of its tile.
-__global__ __launch_bounds__(kSpThreads) void scan_apply_kernel(int32_t* v, int64_t n,
-                                                                const int32_t* sums) {
-  __shared__ int32_t red[kSpWaves + 1];
-  const int64_t first = (int64_t)blockIdx.x * kSpScanTile + (int64_t)threadIdx.x * kSpScanItems;
-  int32_t x[kSpScanItems], s = 0;
-#pragma unroll
-  for (int q = 0; q < kSpScanItems; ++q) {
-    x[q] = first + q < n ? v[first + q] : 0;
-    s += x[q];
-  }
-  int32_t total;
-  int32_t run = sums[blockIdx.x] + block_exclusive(s, red, total);
-#pragma unroll
-  for (int q = 0; q < kSpScanItems; ++q) {
-    if (first + q < n) v[first + q] = run;
-    run += x[q];
-  }
 }
 
 // ----------------------------------------------------------------------------------- sampler
@@ -361,6 +240,20 @@ __global__ __launch_bounds__(kSpThreads) void sample_kernel(const SampleArgs a) 
 }
 
 // -------------------------------------------------------------------------------- compaction
+constexpr int32_t kNewColumn = INT_MAX - 1;  // a sampled column that is no seed
+constexpr int32_t kNoColumn = INT_MAX;       // a column the block does not hold
+
+// Item c of the compaction's scan: whether column c is a new one, and whether it is a seed.
+struct ColumnItem {
+  static constexpr int kSums = 2;
+  const int32_t* mark;
+  __device__ __forceinline__ void operator()(int64_t c, int32_t (&s)[2]) const {
+    const int32_t x = mark[c];
+    s[0] += (int32_t)(x == kNewColumn);
+    s[1] += (int32_t)(x < kNewColumn);
+  }
+};
+
 struct CompactArgs {
   const int32_t* seeds;
   const int32_t* cols;
@@ -393,23 +286,27 @@ __global__ __launch_bounds__(kSpThreads) void compact_mark_kernel(const CompactA
   }
 }
 
-// The new columns in ascending order behind the seeds; counts = {num_src, distinct_seeds}.
+// The new columns in ascending order behind the seeds; counts = {num_src, distinct_seeds}. A
+// thread owns the items of the scan's apply step: sums are the scanned tile sums of the new
+// columns, totals = {new columns, seed columns}.
 __global__ __launch_bounds__(kSpThreads) void compact_place_kernel(const CompactArgs a,
                                                                    const int32_t* sums,
                                                                    const int32_t* totals) {
-  __shared__ int32_t red[kSpWaves + 1];
-  const int64_t first = (int64_t)blockIdx.x * kSpScanTile + (int64_t)threadIdx.x * kSpScanItems;
-  bool fresh[kSpScanItems];
+  constexpr int kItems = maxk_scan::kItems;
+  static_assert(kSpThreads == maxk_scan::kThreads, "a work-group of the scan's shape");
+  __shared__ int32_t red[maxk_scan::kWaves];
+  const int64_t first = (int64_t)blockIdx.x * maxk_scan::kTile + (int64_t)threadIdx.x * kItems;
+  bool fresh[kItems];
   int32_t s = 0;
 #pragma unroll
-  for (int q = 0; q < kSpScanItems; ++q) {
+  for (int q = 0; q < kItems; ++q) {
     fresh[q] = first + q < a.num_cols && a.mark[first + q] == kNewColumn;
     s += (int32_t)fresh[q];
   }
   int32_t total;
   int64_t run = (int64_t)a.S + sums[blockIdx.x] + block_exclusive(s, red, total);
 #pragma unroll
-  for (int q = 0; q < kSpScanItems; ++q) {
+  for (int q = 0; q < kItems; ++q) {
     if (!fresh[q]) continue;
     a.mark[first + q] = (int32_t)run;
     if (run < a.capacity) a.src_ids[run] = (int32_t)(first + q);
@@ -427,33 +324,10 @@ __global__ __launch_bounds__(kSpThreads) void compact_relabel_kernel(const Compa
 }
 
 // ------------------------------------------------------------------------------ entry points
-static int64_t scan_tiles(int64_t n) { return (n + kSpScanTile - 1) / kSpScanTile; }
 static unsigned blocks_of(int64_t n) { return (unsigned)((n + kSpThreads - 1) / kSpThreads); }
 
 // partial sums of the tiles (two arrays) and the totals pair, in int32 words
-static int64_t scan_words(int64_t n) { return 2 * scan_tiles(n) + 2; }
-
-struct Range {
-  const void* p;
-  int64_t bytes;
-};
-
-static int check_ranges(const std::string& w, const Range* ins, int nin, const Range* outs,
-                        int nout) {
-  bool null = false;
-  for (int i = 0; i < nin; ++i) null = null || (ins[i].bytes > 0 && !ins[i].p);
-  for (int i = 0; i < nout; ++i) null = null || (outs[i].bytes > 0 && !outs[i].p);
-  MAXK_CHECK_ARG(!null, w + "null pointer");
-  bool overlap = false;
-  for (int o = 0; o < nout; ++o) {
-    for (int i = 0; i < nin; ++i)
-      overlap = overlap || ranges_overlap(outs[o].p, outs[o].bytes, ins[i].p, ins[i].bytes);
-    for (int i = o + 1; i < nout; ++i)
-      overlap = overlap || ranges_overlap(outs[o].p, outs[o].bytes, outs[i].p, outs[i].bytes);
-  }
-  MAXK_CHECK_ARG(!overlap, w + "an output overlaps an input or another output");
-  return MAXK_OK;
-}
+static int64_t scan_words(int64_t n) { return 2 * maxk_scan::tiles(n) + 2; }
 
 static int sample_impl(const int32_t* ptr, const int32_t* idx, const int32_t* seeds,
                        int32_t* out_ptr, int32_t* out_col, int32_t* out_eid, int64_t capacity,
@@ -483,16 +357,9 @@ static int sample_impl(const int32_t* ptr, const int32_t* idx, const int32_t* se
   }
   const SampleArgs a{ptr, idx, seeds, out_ptr, out_col, out_eid, S, num_rows, E, capacity,
                      fanout, (uint32_t)seed, (uint32_t)(seed >> 32)};
-  const int64_t n = (int64_t)S + 1, nb = scan_tiles(n);
-  int32_t* sums = static_cast<int32_t*>(scratch);
-  int32_t* totals = sums + 2 * nb;
+  const int64_t n = (int64_t)S + 1;
   hipLaunchKernelGGL(sample_count_kernel, dim3(blocks_of(n)), dim3(kSpThreads), 0, st, a);
-  hipLaunchKernelGGL(scan_tile_sums_kernel, dim3((unsigned)nb), dim3(kSpThreads), 0, st,
-                     (const int32_t*)out_ptr, n, 0, sums, (int32_t*)nullptr);
-  hipLaunchKernelGGL(scan_partials_kernel, dim3(1), dim3(kSpThreads), 0, st, sums,
-                     (const int32_t*)nullptr, nb, totals);
-  hipLaunchKernelGGL(scan_apply_kernel, dim3((unsigned)nb), dim3(kSpThreads), 0, st, out_ptr, n,
-                     (const int32_t*)sums);
+  maxk_scan::exclusive_scan(out_ptr, n, static_cast<int32_t*>(scratch), st);
   const dim3 grid((unsigned)(((int64_t)S + kSpTile - 1) / kSpTile));
   if (int e = maxk::dispatch_variant(
           kSampleVariants, select_sample_variant(fanout), [&](auto i) -> int {
@@ -530,9 +397,8 @@ static int compact_impl(const int32_t* seeds, const int32_t* cols, int32_t* src_
   if (int rc = check_ranges(w, ins, 2, outs, 4)) return rc;
   hipStream_t st = (hipStream_t)stream;
   int32_t* mark = static_cast<int32_t*>(scratch);
-  const int64_t nb = scan_tiles(num_cols);
-  int32_t* sums = mark + num_cols;
-  int32_t* seed_sums = sums + nb;
+  const int64_t nb = maxk_scan::tiles(num_cols);
+  int32_t* sums = mark + num_cols;  // [2][nb]: new columns, seed columns
   int32_t* totals = sums + 2 * nb;
   const CompactArgs a{seeds, cols, src_ids, local_col, counts, mark, S, num_cols, M, capacity};
   if (num_cols == 0) {  // no seeds and no edges: {0, 0}
@@ -544,10 +410,8 @@ static int compact_impl(const int32_t* seeds, const int32_t* cols, int32_t* src_
     hipLaunchKernelGGL(compact_mark_kernel, dim3(blocks_of(S)), dim3(kSpThreads), 0, st, a, 0);
   if (M > 0)
     hipLaunchKernelGGL(compact_mark_kernel, dim3(blocks_of(M)), dim3(kSpThreads), 0, st, a, 1);
-  hipLaunchKernelGGL(scan_tile_sums_kernel, dim3((unsigned)nb), dim3(kSpThreads), 0, st,
-                     (const int32_t*)mark, (int64_t)num_cols, 1, sums, seed_sums);
-  hipLaunchKernelGGL(scan_partials_kernel, dim3(1), dim3(kSpThreads), 0, st, sums,
-                     (const int32_t*)seed_sums, nb, totals);
+  maxk_scan::launch_tile_sums(ColumnItem{mark}, (int64_t)num_cols, sums, st);
+  maxk_scan::launch_partials<2>(sums, nb, totals, st);
   hipLaunchKernelGGL(compact_place_kernel, dim3((unsigned)nb), dim3(kSpThreads), 0, st, a,
                      (const int32_t*)sums, (const int32_t*)totals);
   if (M > 0)
@@ -572,9 +436,7 @@ extern "C" int maxk_sample_neighbors(const int32_t* ptr, const int32_t* idx, con
 }
 
 extern "C" int maxk_sample_row_limits(int32_t* out, int32_t capacity) {
-  const int32_t limits[2] = {maxk_sp::kSpShortMax, maxk_sp::kSpMediumMax};
-  for (int i = 0; i < 2 && out && i < capacity; ++i) out[i] = limits[i];
-  return 2;
+  return maxk::copy_limits(out, capacity, {maxk_sp::kSpShortMax, maxk_sp::kSpMediumMax});
 }
 
 extern "C" int64_t maxk_block_compact_scratch_bytes(int32_t num_cols) {

@@ -17,24 +17,22 @@
 // the kernel. Kept edges are counted and placed by popcounts of ballots below the lane, so the
 // order of the edges is the row's and no regime shows in the result.
 //
-// The exclusive sum over the positions runs as three launches on tiles of kSgScanTile items (tile
-// sums, one work-group over the tile sums, apply), the device code of csrc/sample.hip's scan in
-// this namespace; its first two steps also count the distinct nodes and the entries out of range.
+// The exclusive sum over the positions is the shared scan of scan.h; its first two steps also
+// count the distinct nodes and the entries out of range (PositionItem).
 #include <climits>
 
 #include "common.h"
+#include "scan.h"
 #include "variants_subgraph.h"
 
 namespace maxk_sg {
 
-using maxk::ranges_overlap;
+using maxk::check_ranges;
+using maxk::clampi;
+using maxk::Range;
 using maxk::set_error;
 
 constexpr int32_t kNone = INT_MAX;  // mark of a node that is not selected
-
-__device__ __forceinline__ int32_t clampi(int32_t c, int32_t hi) {
-  return c < 0 ? 0 : (c > hi ? hi : c);
-}
 
 struct SubArgs {
   const int32_t* ptr;
@@ -49,19 +47,10 @@ struct SubArgs {
   int64_t E, capacity;
 };
 
-// Segment [lo, hi) of the row that position i names; ptr is clamped into [0, E] and the node
-// into [0, N) (memory safety; the clamped node is the defined one, see the header).
+// Segment [lo, hi) of the row that position i names, clamped (memory safety; the clamped node is
+// the defined one, see the header).
 __device__ __forceinline__ void row_segment(const SubArgs& a, int64_t i, int64_t& lo, int64_t& hi) {
-  lo = 0;
-  hi = 0;
-  if (i < a.S) {
-    const int32_t r = clampi(a.nodes[i], a.N - 1);
-    int64_t b = a.ptr[r], e = a.ptr[r + 1];
-    b = b < 0 ? 0 : (b > a.E ? a.E : b);
-    e = e < b ? b : (e > a.E ? a.E : e);
-    lo = b;
-    hi = e;
-  }
+  maxk::clamped_segment(a.ptr, a.nodes, i, a.S, a.N, a.E, lo, hi);
 }
 
 // The 16-byte boundary of idx at or below edge lo, as an edge number (it may be negative by up
@@ -256,154 +245,31 @@ __global__ __launch_bounds__(kSgThreads) void subgraph_rows_kernel(const SubArgs
   }
 }
 
-// ---------------------------------------------------------------------------------- scans
-__device__ __forceinline__ int32_t wave_sum(int32_t v) {
-#pragma unroll
-  for (int m = 1; m < kSgWave; m <<= 1) v += __shfl_xor(v, m, kSgWave);
-  return v;
-}
-
-// Of tile b of the positions 0 .. S: sums[b] = its kept edges, firsts[b] = the positions that
-// are the lowest of their node, strays[b] = the entries of nodes outside [0, N).
-__global__ __launch_bounds__(kSgThreads) void scan_tile_sums_kernel(const SubArgs a, int32_t* sums,
-                                                                    int32_t* firsts,
-                                                                    int32_t* strays) {
-  __shared__ int32_t red[3][kSgWaves];
-  const int tid = threadIdx.x;
-  const int64_t base = (int64_t)blockIdx.x * kSgScanTile;
-  int32_t s = 0, f = 0, o = 0;
-  for (int q = 0; q < kSgScanItems; ++q) {
-    const int64_t i = base + (int64_t)q * kSgThreads + tid;
-    if (i <= a.S) s += a.out_ptr[i];
-    if (i < a.S) {
-      const int32_t x = a.nodes[i];
-      f += (int32_t)(a.mark[clampi(x, a.N - 1)] == (int32_t)i);
-      o += (int32_t)(x < 0 || x >= a.N);
+// ---------------------------------------------------------------------------------- scan
+// Item i of the scan over the positions 0 .. S: the kept edges of position i, and for i < S
+// whether position i is the lowest of its node, and whether its entry lies outside [0, N).
+struct PositionItem {
+  static constexpr int kSums = 3;
+  const int32_t* out_ptr;
+  const int32_t* nodes;
+  const int32_t* mark;
+  int32_t S, N;
+  __device__ __forceinline__ void operator()(int64_t i, int32_t (&s)[3]) const {
+    s[0] += out_ptr[i];
+    if (i < S) {
+      const int32_t x = nodes[i];
+      s[1] += (int32_t)(mark[clampi(x, N - 1)] == (int32_t)i);
+      s[2] += (int32_t)(x < 0 || x >= N);
     }
   }
-  s = wave_sum(s);
-  f = wave_sum(f);
-  o = wave_sum(o);
-  if ((tid & (kSgWave - 1)) == 0) {
-    red[0][tid / kSgWave] = s;
-    red[1][tid / kSgWave] = f;
-    red[2][tid / kSgWave] = o;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    sums[blockIdx.x] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-    firsts[blockIdx.x] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-    strays[blockIdx.x] = (red[2][0] + red[2][1]) + (red[2][2] + red[2][3]);
-  }
-}
-
-// Exclusive scan of the calling work-group's 256 values: returns the sum of the values of the
-// threads below, and the total in `total`. red: kSgWaves + 1 words of LDS, free on entry.
-__device__ __forceinline__ int32_t block_exclusive(int32_t v, int32_t* red, int32_t& total) {
-  const int tid = threadIdx.x, lane = tid & (kSgWave - 1), wave = tid / kSgWave;
-  int32_t inc = v;
-#pragma unroll
-  for (int m = 1; m < kSgWave; m <<= 1) {
-    const int32_t o = __shfl_up(inc, m, kSgWave);
-    if (lane >= m) inc += o;
-  }
-  if (lane == kSgWave - 1) red[wave] = inc;
-  __syncthreads();
-  int32_t before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < kSgWaves; ++w) {
-    const int32_t x = red[w];
-    before += w < wave ? x : 0;
-    all += x;
-  }
-  total = all;
-  __syncthreads();  // red is free again
-  return before + inc - v;
-}
-
-// One work-group: sums[0 .. nb) becomes its exclusive scan; counts = {the grand total M, the
-// distinct nodes, the entries out of range}.
-__global__ __launch_bounds__(kSgThreads) void scan_partials_kernel(int32_t* sums,
-                                                                   const int32_t* firsts,
-                                                                   const int32_t* strays,
-                                                                   int64_t nb, int32_t* counts) {
-  __shared__ int32_t red[kSgWaves + 1];
-  __shared__ int32_t tot[2][kSgWaves];
-  const int tid = threadIdx.x;
-  int32_t carry = 0, first = 0, stray = 0;  // first, stray: this thread's share of the totals
-  for (int64_t i0 = 0; i0 < nb; i0 += kSgThreads) {
-    const int64_t i = i0 + tid;
-    int32_t total;
-    const int32_t ex = block_exclusive(i < nb ? sums[i] : 0, red, total);
-    if (i < nb) {
-      sums[i] = carry + ex;
-      first += firsts[i];
-      stray += strays[i];
-    }
-    carry += total;
-  }
-  first = wave_sum(first);
-  stray = wave_sum(stray);
-  if ((tid & (kSgWave - 1)) == 0) {
-    tot[0][tid / kSgWave] = first;
-    tot[1][tid / kSgWave] = stray;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    counts[0] = carry;
-    counts[1] = (tot[0][0] + tot[0][1]) + (tot[0][2] + tot[0][3]);
-    counts[2] = (tot[1][0] + tot[1][1]) + (tot[1][2] + tot[1][3]);
-  }
-}
-
-// v[0 .. n) becomes its exclusive scan, in place: a thread owns kSgScanItems consecutive items
-// of its tile.
-__global__ __launch_bounds__(kSgThreads) void scan_apply_kernel(int32_t* v, int64_t n,
-                                                                const int32_t* sums) {
-  __shared__ int32_t red[kSgWaves + 1];
-  const int64_t first = (int64_t)blockIdx.x * kSgScanTile + (int64_t)threadIdx.x * kSgScanItems;
-  int32_t x[kSgScanItems], s = 0;
-#pragma unroll
-  for (int q = 0; q < kSgScanItems; ++q) {
-    x[q] = first + q < n ? v[first + q] : 0;
-    s += x[q];
-  }
-  int32_t total;
-  int32_t run = sums[blockIdx.x] + block_exclusive(s, red, total);
-#pragma unroll
-  for (int q = 0; q < kSgScanItems; ++q) {
-    if (first + q < n) v[first + q] = run;
-    run += x[q];
-  }
-}
+};
 
 // ------------------------------------------------------------------------------ entry points
-static int64_t scan_tiles(int64_t n) { return (n + kSgScanTile - 1) / kSgScanTile; }
 static unsigned blocks_of(int64_t n) { return (unsigned)((n + kSgThreads - 1) / kSgThreads); }
 
 // one int32 per node, and three sums per tile of the positions 0 .. S
-static int64_t scratch_bytes_of(int64_t N, int64_t S) { return 4 * (N + 3 * scan_tiles(S + 1)); }
-
-struct Range {
-  const void* p;
-  int64_t bytes;
-};
-
-static int check_ranges(const std::string& w, const Range* ins, int nin, const Range* outs,
-                        int nout) {
-  bool null = false;
-  for (int i = 0; i < nin; ++i) null = null || (ins[i].bytes > 0 && !ins[i].p);
-  for (int i = 0; i < nout; ++i) null = null || (outs[i].bytes > 0 && !outs[i].p);
-  MAXK_CHECK_ARG(!null, w + "null pointer");
-  bool overlap = false;
-  for (int o = 0; o < nout; ++o) {
-    for (int i = 0; i < nin; ++i)
-      overlap = overlap || ranges_overlap(outs[o].p, outs[o].bytes, ins[i].p, ins[i].bytes);
-    for (int i = o + 1; i < nout; ++i)
-      overlap = overlap || ranges_overlap(outs[o].p, outs[o].bytes, outs[i].p, outs[i].bytes);
-  }
-  MAXK_CHECK_ARG(!overlap, w + "an output overlaps an input or another output");
-  return MAXK_OK;
+static int64_t scratch_bytes_of(int64_t N, int64_t S) {
+  return 4 * (N + PositionItem::kSums * maxk_scan::tiles(S + 1));
 }
 
 static int check_sizes(const std::string& w, int32_t N, int64_t E, int32_t S, int64_t capacity,
@@ -452,17 +318,14 @@ static int count_impl(const int32_t* ptr, const int32_t* idx, const int32_t* nod
     return MAXK_OK;
   }
   int32_t* mark = static_cast<int32_t*>(scratch);
-  const int64_t n = (int64_t)S + 1, nb = scan_tiles(n);
-  int32_t* sums = mark + N;
+  const int64_t n = (int64_t)S + 1;
+  int32_t* sums = mark + N;  // [3][tiles]: kept edges, first positions, strays
   const SubArgs a{ptr, idx, nodes, out_ptr, nullptr, nullptr, counts, mark, S, N, E, 0};
   launch_marks(a, st);
   if (int e = launch_rows(a, false, st)) return e;
-  hipLaunchKernelGGL(scan_tile_sums_kernel, dim3((unsigned)nb), dim3(kSgThreads), 0, st, a, sums,
-                     sums + nb, sums + 2 * nb);
-  hipLaunchKernelGGL(scan_partials_kernel, dim3(1), dim3(kSgThreads), 0, st, sums,
-                     (const int32_t*)(sums + nb), (const int32_t*)(sums + 2 * nb), nb, counts);
-  hipLaunchKernelGGL(scan_apply_kernel, dim3((unsigned)nb), dim3(kSgThreads), 0, st, out_ptr, n,
-                     (const int32_t*)sums);
+  maxk_scan::launch_tile_sums(PositionItem{out_ptr, nodes, mark, S, N}, n, sums, st);
+  maxk_scan::launch_partials<3>(sums, maxk_scan::tiles(n), counts, st);
+  maxk_scan::launch_apply(out_ptr, n, sums, st);
   MAXK_LAUNCH_CHECK("maxk_induced_subgraph_count launch");
   return MAXK_OK;
 }
@@ -517,7 +380,5 @@ extern "C" int maxk_induced_subgraph_fill(const int32_t* ptr, const int32_t* idx
 }
 
 extern "C" int maxk_subgraph_row_limits(int32_t* out, int32_t capacity) {
-  const int32_t limits[2] = {maxk_sg::kSgShortMax, maxk_sg::kSgMediumMax};
-  for (int i = 0; i < 2 && out && i < capacity; ++i) out[i] = limits[i];
-  return 2;
+  return maxk::copy_limits(out, capacity, {maxk_sg::kSgShortMax, maxk_sg::kSgMediumMax});
 }

@@ -9,8 +9,8 @@
 //                        rows, and writes its digit counts digit-major, hist[digit][tile]; pass 0
 //                        also counts the columns into out_ptr (integer atomics whose results are
 //                        not read; their sums are read after a launch boundary)
-//   scan (3 launches)    hist becomes its exclusive scan: the place of the first item of digit d
-//                        of tile t in the pass's output
+//   scan (3 launches)    hist becomes its exclusive scan (scan.h): the place of the first item
+//                        of digit d of tile t in the pass's output
 //   scatter_pass_kernel  wave w of a tile owns the sub-run w of kTrSubRun consecutive items. The
 //                        waves count their sub-runs' digits again (LDS atomics, sums only), the
 //                        counts of the waves below and the tile's scanned base give each wave a
@@ -28,16 +28,15 @@
 #include <climits>
 
 #include "common.h"
+#include "scan.h"
 #include "variants_transpose.h"
 
 namespace maxk_tr {
 
-using maxk::ranges_overlap;
+using maxk::check_ranges;
+using maxk::clampi;
+using maxk::Range;
 using maxk::set_error;
-
-__device__ __forceinline__ int32_t clampi(int32_t c, int32_t hi) {
-  return c < 0 ? 0 : (c > hi ? hi : c);
-}
 
 struct TrArgs {
   const int32_t* ptr;
@@ -198,91 +197,7 @@ __global__ __launch_bounds__(kTrThreads) void zero_kernel(int32_t* v, int64_t n)
   if (i < n) v[i] = 0;
 }
 
-// ---------------------------------------------------------------------------------- scans
-// The three-launch exclusive scan of csrc/sample.hip and csrc/subgraph.hip, in this namespace.
-__device__ __forceinline__ int32_t wave_sum(int32_t v) {
-#pragma unroll
-  for (int m = 1; m < kTrWave; m <<= 1) v += __shfl_xor(v, m, kTrWave);
-  return v;
-}
-
-__global__ __launch_bounds__(kTrThreads) void scan_tile_sums_kernel(const int32_t* v, int64_t n,
-                                                                    int32_t* sums) {
-  __shared__ int32_t red[kTrWaves];
-  const int tid = threadIdx.x;
-  const int64_t base = (int64_t)blockIdx.x * kTrScanTile;
-  int32_t s = 0;
-  for (int q = 0; q < kTrScanItems; ++q) {
-    const int64_t i = base + (int64_t)q * kTrThreads + tid;
-    if (i < n) s += v[i];
-  }
-  s = wave_sum(s);
-  if ((tid & (kTrWave - 1)) == 0) red[tid / kTrWave] = s;
-  __syncthreads();
-  if (tid == 0) sums[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// Exclusive scan of the calling work-group's 256 values: returns the sum of the values of the
-// threads below, and the total in `total`. red: kTrWaves words of LDS, free on entry.
-__device__ __forceinline__ int32_t block_exclusive(int32_t v, int32_t* red, int32_t& total) {
-  const int tid = threadIdx.x, lane = tid & (kTrWave - 1), wave = tid / kTrWave;
-  int32_t inc = v;
-#pragma unroll
-  for (int m = 1; m < kTrWave; m <<= 1) {
-    const int32_t o = __shfl_up(inc, m, kTrWave);
-    if (lane >= m) inc += o;
-  }
-  if (lane == kTrWave - 1) red[wave] = inc;
-  __syncthreads();
-  int32_t before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < kTrWaves; ++w) {
-    const int32_t x = red[w];
-    before += w < wave ? x : 0;
-    all += x;
-  }
-  total = all;
-  __syncthreads();  // red is free again
-  return before + inc - v;
-}
-
-// One work-group: sums[0 .. nb) becomes its exclusive scan.
-__global__ __launch_bounds__(kTrThreads) void scan_partials_kernel(int32_t* sums, int64_t nb) {
-  __shared__ int32_t red[kTrWaves];
-  const int tid = threadIdx.x;
-  int32_t carry = 0;
-  for (int64_t i0 = 0; i0 < nb; i0 += kTrThreads) {
-    const int64_t i = i0 + tid;
-    int32_t total;
-    const int32_t ex = block_exclusive(i < nb ? sums[i] : 0, red, total);
-    if (i < nb) sums[i] = carry + ex;
-    carry += total;
-  }
-}
-
-// v[0 .. n) becomes its exclusive scan, in place: a thread owns kTrScanItems consecutive items
-// of its tile.
-__global__ __launch_bounds__(kTrThreads) void scan_apply_kernel(int32_t* v, int64_t n,
-                                                                const int32_t* sums) {
-  __shared__ int32_t red[kTrWaves];
-  const int64_t first = (int64_t)blockIdx.x * kTrScanTile + (int64_t)threadIdx.x * kTrScanItems;
-  int32_t x[kTrScanItems], s = 0;
-#pragma unroll
-  for (int q = 0; q < kTrScanItems; ++q) {
-    x[q] = first + q < n ? v[first + q] : 0;
-    s += x[q];
-  }
-  int32_t total;
-  int32_t run = sums[blockIdx.x] + block_exclusive(s, red, total);
-#pragma unroll
-  for (int q = 0; q < kTrScanItems; ++q) {
-    if (first + q < n) v[first + q] = run;
-    run += x[q];
-  }
-}
-
 // ------------------------------------------------------------------------------ entry points
-static int64_t scan_tiles(int64_t n) { return (n + kTrScanTile - 1) / kTrScanTile; }
 static int64_t tiles_of(int64_t E) { return (E + kTrTile - 1) / kTrTile; }
 
 // The (column, edge) buffer of a sort of more than one pass, the tile histograms of the widest
@@ -293,22 +208,8 @@ static int64_t scratch_bytes_of(int64_t NC, int64_t E) {
   const int64_t pairs = pass_count(nc) > 1 ? 8 * E : 0;
   const int64_t hist = tiles_of(E) << digit_bits(nc, 0);
   const int64_t longest = hist > NC + 1 ? hist : NC + 1;
-  return pairs + 4 * (hist + scan_tiles(longest));
+  return pairs + 4 * (hist + maxk_scan::tiles(longest));
 }
-
-static void launch_scan(int32_t* v, int64_t n, int32_t* sums, hipStream_t st) {
-  const int64_t nb = scan_tiles(n);
-  hipLaunchKernelGGL(scan_tile_sums_kernel, dim3((unsigned)nb), dim3(kTrThreads), 0, st,
-                     (const int32_t*)v, n, sums);
-  hipLaunchKernelGGL(scan_partials_kernel, dim3(1), dim3(kTrThreads), 0, st, sums, nb);
-  hipLaunchKernelGGL(scan_apply_kernel, dim3((unsigned)nb), dim3(kTrThreads), 0, st, v, n,
-                     (const int32_t*)sums);
-}
-
-struct Range {
-  const void* p;
-  int64_t bytes;
-};
 
 static int transpose_impl(const int32_t* ptr, const int32_t* idx, const float* val,
                           int32_t* out_ptr, int32_t* out_row, int32_t* out_order, float* out_val,
@@ -332,17 +233,7 @@ static int transpose_impl(const int32_t* ptr, const int32_t* idx, const float* v
                         {val, val ? 4 * E : 0}};
   const Range outs[5] = {{out_ptr, 4 * ((int64_t)NC + 1)}, {out_row, 4 * E}, {out_order, 4 * E},
                          {out_val, out_val ? 4 * E : 0},   {scratch, need}};
-  bool null = false, overlap = false;
-  for (const Range& r : ins) null = null || (r.bytes > 0 && !r.p);
-  for (const Range& r : outs) null = null || (r.bytes > 0 && !r.p);
-  MAXK_CHECK_ARG(!null, w + "null pointer");
-  for (int o = 0; o < 5; ++o) {
-    for (int i = 0; i < 3; ++i)
-      overlap = overlap || ranges_overlap(outs[o].p, outs[o].bytes, ins[i].p, ins[i].bytes);
-    for (int i = o + 1; i < 5; ++i)
-      overlap = overlap || ranges_overlap(outs[o].p, outs[o].bytes, outs[i].p, outs[i].bytes);
-  }
-  MAXK_CHECK_ARG(!overlap, w + "an output overlaps an input or another output");
+  if (int rc = check_ranges(w, ins, 3, outs, 5)) return rc;
 
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(zero_kernel, dim3((unsigned)(((int64_t)NC + kTrThreads) / kTrThreads)),
@@ -380,7 +271,7 @@ static int transpose_impl(const int32_t* ptr, const int32_t* idx, const float* v
               return MAXK_OK;
             }))
       return e;
-    launch_scan(hist, tiles << a.bits, sums, st);
+    maxk_scan::exclusive_scan(hist, tiles << a.bits, sums, st);
     if (int e = maxk::dispatch_variant(
             kPassVariants, select_pass_variant(pass, passes, val != nullptr),
             [&](auto i) -> int {
@@ -390,7 +281,7 @@ static int transpose_impl(const int32_t* ptr, const int32_t* idx, const float* v
             }))
       return e;
   }
-  launch_scan(out_ptr, (int64_t)NC + 1, sums, st);
+  maxk_scan::exclusive_scan(out_ptr, (int64_t)NC + 1, sums, st);
   MAXK_LAUNCH_CHECK("maxk_csr_transpose launch");
   return MAXK_OK;
 }

@@ -21,9 +21,6 @@ constexpr int kSpGroup = 16;                     // lanes of a lane group: one s
 constexpr int kSpShortMax = kSpGroup;
 constexpr int kSpSlots = 8;
 constexpr int kSpMediumMax = kSpWave * kSpSlots;
-// The scans (exclusive sums over the seeds, over the columns) run on tiles of this many items.
-constexpr int kSpScanItems = 8;
-constexpr int kSpScanTile = kSpThreads * kSpScanItems;
 
 // sample_kernel<ALL>: ALL = every edge of every seed is kept (fanout < 0), no selection code
 struct SampleVariant {

@@ -29,9 +29,6 @@ constexpr int kSgMediumMax = 512;
 constexpr int kSgMediumChunks = (kSgMediumMax + kSgQuad - 1 + kSgChunk - 1) / kSgChunk;
 constexpr int kSgHubChunks = 2;
 constexpr int kSgHubPass = kSgWaves * kSgHubChunks * kSgChunk;   // edges of a work-group pass
-// The scan (exclusive sums over the positions) runs on tiles of this many items.
-constexpr int kSgScanItems = 8;
-constexpr int kSgScanTile = kSgThreads * kSgScanItems;
 
 // subgraph_rows_kernel<FILL>: false counts the kept edges of every position (out_ptr before its
 // scan), true places them (out_col, out_eid) behind the scanned out_ptr

@@ -26,9 +26,6 @@ constexpr int kTrTile = kTrWaves * kTrSubRun;    // 8,192 items of a work-group
 constexpr int kTrMaxDigitBits = 11;
 constexpr int kTrMaxDigits = 1 << kTrMaxDigitBits;
 constexpr int kTrMaxPasses = 3;                  // 31 key bits in digits of at most 11
-// The scans (tile histograms, column counts) run on tiles of this many items.
-constexpr int kTrScanItems = 8;
-constexpr int kTrScanTile = kTrThreads * kTrScanItems;
 
 // Bits of the sort key: columns are in [0, num_cols), so bits(num_cols - 1); 0 for one column.
 constexpr int key_bits(int32_t num_cols) {

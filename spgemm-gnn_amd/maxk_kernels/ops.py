@@ -794,14 +794,20 @@ def edge_softmax_backward(ptr, y, grad_y, out: Optional[torch.Tensor] = None) ->
     return out
 
 
+def _int32_list(fn, *args) -> Tuple[int, ...]:
+    """The list behind an export ``fn(*args, out, capacity) -> count``: asked for its count, then
+    read in full."""
+    count = fn(*args, None, 0)
+    buf = (ctypes.c_int32 * count)()
+    fn(*args, ctypes.cast(buf, ctypes.c_void_p), count)
+    return tuple(int(v) for v in buf)
+
+
 def edge_softmax_row_limits() -> Tuple[int, ...]:
     """The row lengths at which the edge-softmax kernels switch regime, ascending
     (``maxk_edge_softmax_row_limits``): a row of exactly a limit's length runs in the regime
     below it."""
-    count = lib.maxk_edge_softmax_row_limits(None, 0)
-    buf = (ctypes.c_int32 * count)()
-    lib.maxk_edge_softmax_row_limits(ctypes.cast(buf, ctypes.c_void_p), count)
-    return tuple(int(v) for v in buf)
+    return _int32_list(lib.maxk_edge_softmax_row_limits)
 
 
 def _vector(t, name: str, dtype: torch.dtype, size, size_name: str, dev) -> None:
@@ -1055,10 +1061,7 @@ def heads_row_limits() -> Tuple[int, ...]:
     """``(row_short, row_medium, col_short, col_medium)``: the row lengths at which the
     multi-head forward and the column lengths at which its backward switch regime
     (``maxk_heads_row_limits``); exactly a limit's length runs in the regime below it."""
-    count = lib.maxk_heads_row_limits(None, 0)
-    buf = (ctypes.c_int32 * count)()
-    lib.maxk_heads_row_limits(ctypes.cast(buf, ctypes.c_void_p), count)
-    return tuple(int(v) for v in buf)
+    return _int32_list(lib.maxk_heads_row_limits)
 
 
 # -------------------------------------------------------------------------------------
@@ -1132,10 +1135,7 @@ def max_aggregate_backward(ptr_t, idx_t, order, grad_out, arg_edge, arg_slot,
 def max_row_limits() -> Tuple[int, ...]:
     """``(row_short, row_medium, col_short, col_medium)`` of the max aggregation's forward and
     backward (``maxk_max_row_limits``); exactly a limit's length runs in the regime below it."""
-    count = lib.maxk_max_row_limits(None, 0)
-    buf = (ctypes.c_int32 * count)()
-    lib.maxk_max_row_limits(ctypes.cast(buf, ctypes.c_void_p), count)
-    return tuple(int(v) for v in buf)
+    return _int32_list(lib.maxk_max_row_limits)
 
 
 # -------------------------------------------------------------------------------------
@@ -1231,10 +1231,7 @@ def block_compact(seeds, cols, num_cols: int, out=None, scratch=None):
 def sample_row_limits() -> Tuple[int, ...]:
     """``(short, medium)``: the row lengths at which the sampler switches regime
     (``maxk_sample_row_limits``); exactly a limit's length runs in the regime below it."""
-    count = lib.maxk_sample_row_limits(None, 0)
-    buf = (ctypes.c_int32 * count)()
-    lib.maxk_sample_row_limits(ctypes.cast(buf, ctypes.c_void_p), count)
-    return tuple(int(v) for v in buf)
+    return _int32_list(lib.maxk_sample_row_limits)
 
 
 # -------------------------------------------------------------------------------------
@@ -1303,10 +1300,7 @@ def induced_subgraph_fill(ptr, idx, nodes, out_ptr, capacity: Optional[int] = No
 def subgraph_row_limits() -> Tuple[int, ...]:
     """``(short, medium)``: the row lengths at which the extraction switches regime
     (``maxk_subgraph_row_limits``); exactly a limit's length runs in the regime below it."""
-    count = lib.maxk_subgraph_row_limits(None, 0)
-    buf = (ctypes.c_int32 * count)()
-    lib.maxk_subgraph_row_limits(ctypes.cast(buf, ctypes.c_void_p), count)
-    return tuple(int(v) for v in buf)
+    return _int32_list(lib.maxk_subgraph_row_limits)
 
 
 # -------------------------------------------------------------------------------------
@@ -1320,10 +1314,7 @@ def csr_transpose_scratch_bytes(num_rows: int, num_cols: int, num_edges: int) ->
 def transpose_digit_bits(num_cols: int) -> Tuple[int, ...]:
     """The digit widths, lowest digit first, of the radix passes :func:`csr_transpose` runs for
     ``num_cols`` columns (``maxk_transpose_digit_bits``)."""
-    count = lib.maxk_transpose_digit_bits(int(num_cols), None, 0)
-    buf = (ctypes.c_int32 * count)()
-    lib.maxk_transpose_digit_bits(int(num_cols), ctypes.cast(buf, ctypes.c_void_p), count)
-    return tuple(int(v) for v in buf)
+    return _int32_list(lib.maxk_transpose_digit_bits, int(num_cols))
 
 
 def csr_transpose(ptr, idx, val=None, num_cols: Optional[int] = None, out=None, scratch=None):

@@ -10,6 +10,7 @@ import functools
 import numpy as np
 
 import gat_heads as gh
+import scan
 from gat_heads import NUM, bound, exact_grad, rows_of  # noqa: F401  (used by the test modules)
 
 LIMITS = (16, 512)               # maxk_sample_row_limits, asserted against the library
@@ -17,11 +18,14 @@ FANOUTS = (1, 2, 10, 25, 64)     # and one above the longest row, and -1 (every 
 M32 = np.uint64(0xFFFFFFFF)
 KERNELS = ("maxk_sp::compact_init_kernel", "maxk_sp::compact_mark_kernel",
            "maxk_sp::compact_place_kernel", "maxk_sp::compact_relabel_kernel",
-           "maxk_sp::sample_count_kernel", "maxk_sp::scan_apply_kernel",
-           "maxk_sp::scan_partials_kernel", "maxk_sp::scan_tile_sums_kernel")
-SAMPLER_KERNELS = KERNELS[4:]
-COMPACT_KERNELS = KERNELS[:4] + KERNELS[6:]
-SCAN_TILE = 2048                 # items of a scan tile (csrc/variants_sample.h)
+           "maxk_sp::sample_count_kernel")
+# the maxk_scan:: kernels of the compaction: its tile sums count new and seed columns
+COMPACT_SCAN_KERNELS = ("maxk_scan::partials_kernel<2>",
+                        "maxk_scan::tile_sums_kernel<maxk_sp::ColumnItem>")
+SCAN_KERNELS = scan.PLAIN_KERNELS + COMPACT_SCAN_KERNELS     # every maxk_scan:: name restated here
+SAMPLER_KERNELS = KERNELS[4:] + scan.PLAIN_KERNELS
+COMPACT_KERNELS = KERNELS[:4] + COMPACT_SCAN_KERNELS
+SCAN_TILE = scan.TILE            # items of a scan tile (csrc/scan.h)
 
 
 def sample_kernel_name(fanout):

@@ -12,15 +12,17 @@ import torch
 import torch.nn.functional as F
 
 import gat_heads as gh
+import scan
 from gat_heads import ND, NUM, rows_of  # noqa: F401  (used by the test modules)
 
 LIMITS = (16, 512)               # maxk_subgraph_row_limits, asserted against the library
 NONE = 2 ** 31 - 1               # local(c) of a node that is not selected
-SCAN_TILE = 2048                 # positions of a scan tile (csrc/variants_subgraph.h)
+SCAN_TILE = scan.TILE            # positions of a scan tile (csrc/scan.h)
 SHARED_KERNELS = ("maxk_sg::mark_init_kernel", "maxk_sg::mark_nodes_kernel")
-COUNT_KERNELS = SHARED_KERNELS + ("maxk_sg::scan_apply_kernel", "maxk_sg::scan_partials_kernel",
-                                  "maxk_sg::scan_tile_sums_kernel",
-                                  "maxk_sg::subgraph_rows_kernel<false>")
+# the maxk_scan:: kernels of the count: its tile sums also count first positions and strays
+SCAN_KERNELS = ("maxk_scan::apply_kernel", "maxk_scan::partials_kernel<3>",
+                "maxk_scan::tile_sums_kernel<maxk_sg::PositionItem>")
+COUNT_KERNELS = SHARED_KERNELS + SCAN_KERNELS + ("maxk_sg::subgraph_rows_kernel<false>",)
 FILL_KERNELS = SHARED_KERNELS + ("maxk_sg::subgraph_rows_kernel<true>",)
 KERNELS = tuple(sorted(set(COUNT_KERNELS) | set(FILL_KERNELS)))
 
@@ -62,6 +64,22 @@ def subgraph_ref(ptr, idx, nodes, num_nodes):
     eid = np.concatenate(eids) if eids else np.zeros(0, np.int64)
     return (out_ptr.astype(np.int32), col.astype(np.int32), eid.astype(np.int32),
             (int(out_ptr[-1]), distinct, stray))
+
+
+def count_ref(ptr, idx, nodes, num_nodes):
+    """(out_ptr int32 [S + 1], (M, distinct, stray)) of maxk_induced_subgraph_count without a
+    loop over the positions, for selections too long for subgraph_ref."""
+    raw = np.asarray(nodes, np.int64)
+    stray = int(((raw < 0) | (raw >= num_nodes)).sum())
+    sel = np.clip(raw, 0, max(num_nodes - 1, 0))
+    named = np.unique(sel)
+    selected = np.zeros(max(num_nodes, 1), bool)
+    selected[named] = True
+    kept_of_row = np.bincount(rows_of(ptr), weights=selected[np.asarray(idx, np.int64)],
+                              minlength=num_nodes).astype(np.int64)
+    out_ptr = np.zeros(sel.size + 1, np.int64)
+    np.cumsum(kept_of_row[sel], out=out_ptr[1:])
+    return out_ptr.astype(np.int32), (int(out_ptr[-1]), int(named.size), stray)
 
 
 def dense_of(ptr, idx, num_cols, val=None):

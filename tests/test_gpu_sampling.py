@@ -4,8 +4,9 @@ guarded, poisoned buffers; capture; the block aggregation and its autograd again
 MaxKSAGEConv / MaxKSAGE on blocks. Two graphs serve the module: the 600-row graph of the
 multi-head tests (hub row 5,000, hub column 3,000) and a 300 x 900 rectangular one whose rows sit
 at f - 1, f, f + 1 of every fanout and on both sides of every limit
-(tests/test_sampling_capi.py checks those preconditions). The last test closes over the compiled
-maxk_sp:: instantiations.
+(tests/test_sampling_capi.py checks those preconditions). Both scans run at the lengths of
+tests/scan.py. The last test closes over the compiled maxk_sp:: instantiations and the maxk_scan::
+kernels the two entry points launch.
 
 Worst error / bound figures print with -s."""
 import ctypes
@@ -19,6 +20,7 @@ import torch
 import gat_heads as gh
 import maxk_kernels as mk
 import sampling as sp
+import scan
 from arena import POISONS, arena
 from maxk_kernels import _lib, ops
 
@@ -45,8 +47,9 @@ def same(got, want, what):
 
 
 def compiled():
+    """The maxk_sp:: fixture and the maxk_scan:: kernels the two entry points launch."""
     with open(FIXTURE) as f:
-        return {ln.strip() for ln in f if ln.strip()}
+        return {ln.strip() for ln in f if ln.strip()} | set(sp.SCAN_KERNELS)
 
 
 def sampler_names(fanout):
@@ -588,10 +591,52 @@ def test_two_layer_sage_over_the_sampler_matches_float64(gpu):
     assert any(not torch.equal(a, b) for a, b in zip(before, model.parameters()))
 
 
-# ------------------------------------------------------------------ 7. closure (keep last)
+# ------------------------------------------------------------------ 7. scan lengths
+@pytest.mark.parametrize("n", scan.LENGTHS)
+def test_sampler_scans_n_items(gpu, n):
+    """out_ptr is scanned over S + 1 = n items: S seeds drawn with repetition from the 300-row
+    graph, every neighbour kept, so out_ptr is the cumulative sum of the seeds' row lengths and
+    out_eid the concatenation of their edge ranges."""
+    ptr, idx, _ = sp.rect_graph()
+    ptr_d, idx_d, _ = graph_dev("rect", gpu)
+    seeds = np.random.default_rng(n).integers(0, ptr.size - 1, n - 1).astype(np.int32)
+    lens = np.diff(ptr).astype(np.int64)[seeds]
+    w_ptr = np.zeros(n, np.int64)
+    np.cumsum(lens, out=w_ptr[1:])
+    m = int(w_ptr[-1])
+    assert m < 2 ** 31
+    w_eid = np.arange(m) + np.repeat(ptr[seeds] - w_ptr[:-1], lens)
+    out = tuple(torch.full((size,), -7, dtype=torch.int32, device=gpu) for size in (n, m, m))
+    ops.sample_neighbors(ptr_d, idx_d, dev_of(seeds, gpu), -1, 3, out=out)
+    same(out[0].cpu().numpy(), w_ptr.astype(np.int32), f"{n} items: out_ptr")
+    same(out[2].cpu().numpy(), w_eid.astype(np.int32), f"{n} items: out_eid")
+    same(out[1].cpu().numpy(), idx[w_eid], f"{n} items: out_col")
+    if seeds.size:
+        COVERED.update(sampler_names(-1))
+
+
+@pytest.mark.parametrize("n", scan.LENGTHS)
+def test_compaction_scans_n_columns(gpu, n):
+    """The new columns are counted and placed over num_cols = n items: 300 seeds (below the last
+    column where there is more than one), 3,000 sampled columns over the whole range with the
+    first column, the last one and a seed among them."""
+    rng = np.random.default_rng(n)
+    seeds = rng.choice(max(n - 1, 1), min(300, max(n - 1, 1)), replace=False).astype(np.int32)
+    cols = rng.integers(0, n, 3000).astype(np.int32)
+    cols[:3] = (n - 1, 0, seeds[0])
+    w_src, w_local, w_counts = sp.compact_ref(seeds, cols, n)
+    assert n == 1 or w_src[-1] == n - 1          # the last column is a new one, placed last
+    src, local, counts = ops.block_compact(dev_of(seeds, gpu), dev_of(cols, gpu), n)
+    assert tuple(counts.tolist()) == w_counts, n
+    same(src.cpu().numpy()[:w_counts[0]], w_src, f"{n} columns: src_ids")
+    same(local.cpu().numpy(), w_local, f"{n} columns: local_col")
+    COVERED.update(sp.COMPACT_KERNELS)
+
+
+# ------------------------------------------------------------------ 8. closure (keep last)
 def test_every_sampler_instantiation_was_launched_by_a_passing_case(gpu):
     names = compiled()
-    assert len(names) == 10
+    assert len(names) == 7 + len(sp.SCAN_KERNELS) == 12
     missing = sorted(names - COVERED)
     assert not missing, f"instantiations without a passing case: {missing}"
     assert not COVERED - names

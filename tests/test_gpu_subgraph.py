@@ -4,7 +4,8 @@ capture; every layer on the identity subgraph against the full graph, bit for bi
 half against float64; edge_weight through Subgraph.edge_data; and a MaxKGCN trained over
 ClusterLoader with cached subgraphs and plans. The graph is the 600-row one of the multi-head
 tests (hub row 5,000, hub column 3,000); tests/test_subgraph_capi.py checks the preconditions of
-the node sets. The last test closes over the compiled maxk_sg:: instantiations.
+the node sets. The count's scan runs at the lengths of tests/scan.py. The last test closes over the
+compiled maxk_sg:: instantiations and the maxk_scan:: kernels the count launches.
 
 Worst norm-wise differences print with -s."""
 import ctypes
@@ -16,6 +17,7 @@ import pytest
 import torch
 
 import maxk_kernels as mk
+import scan
 import subgraph as sg
 from arena import POISONS, arena
 from maxk_kernels import _lib, ops
@@ -42,8 +44,9 @@ def same(got, want, what):
 
 
 def compiled():
+    """The maxk_sg:: fixture and the maxk_scan:: kernels the count launches."""
     with open(FIXTURE) as f:
-        return {ln.strip() for ln in f if ln.strip()}
+        return {ln.strip() for ln in f if ln.strip()} | set(sg.SCAN_KERNELS)
 
 
 @functools.lru_cache(maxsize=None)
@@ -485,10 +488,29 @@ def test_two_layer_gcn_trains_over_the_cluster_loader(gpu, monkeypatch):
     COVERED.update(sg.KERNELS)
 
 
-# ------------------------------------------------------------------ 6. closure (keep last)
+# ------------------------------------------------------------------ 6. scan lengths
+@pytest.mark.parametrize("n", scan.LENGTHS)
+def test_count_scans_n_items(gpu, n):
+    """out_ptr is scanned over S + 1 = n items: S positions drawn with repetition from the 600
+    nodes, the last three of them (the last tile of the positions) out of range. counts holds the
+    kept edges, the distinct nodes and the entries out of range."""
+    ptr, idx, num = sg.graph()
+    ptr_d, idx_d = graph_dev(gpu)
+    nodes = np.random.default_rng(n).integers(0, num, n - 1).astype(np.int32)
+    nodes[max(n - 4, 0):] = (num, -1, 2 ** 31 - 1)[:min(3, n - 1)]
+    w_ptr, w_counts = sg.count_ref(ptr, idx, nodes, num)
+    assert w_counts[2] == min(3, n - 1) and w_counts[0] < 2 ** 31
+    out_ptr, counts = ops.induced_subgraph_count(ptr_d, idx_d, dev_of(nodes, gpu))
+    same(out_ptr.cpu().numpy(), w_ptr, f"{n} items: out_ptr")
+    assert tuple(counts.tolist()) == w_counts, (n, counts.tolist(), w_counts)
+    if nodes.size:
+        COVERED.update(sg.COUNT_KERNELS)
+
+
+# ------------------------------------------------------------------ 7. closure (keep last)
 def test_every_subgraph_instantiation_was_launched_by_a_passing_case(gpu):
     names = compiled()
-    assert len(names) == 7
+    assert len(names) == 4 + len(sg.SCAN_KERNELS) == 7
     missing = sorted(names - COVERED)
     assert not missing, f"instantiations without a passing case: {missing}"
     assert not COVERED - names

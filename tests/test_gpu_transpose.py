@@ -3,8 +3,9 @@ four outputs (the rule is part of the ABI); its output contract on guarded, pois
 capture; the wiring of CSRGraph, Block and Subgraph against the torch path they had before; the
 registered operator; and one backward per consumer of A^T, bit-equal between a graph whose
 structure the kernel built and a twin whose structure the torch path built. tests/
-test_transpose_capi.py checks the preconditions of the cases. The last test closes over the
-compiled maxk_tr:: instantiations."""
+test_transpose_capi.py checks the preconditions of the cases. Both scans run at the lengths of
+tests/scan.py. The last test closes over the compiled maxk_tr:: instantiations and the maxk_scan::
+kernels of the plain scan."""
 import ctypes
 import functools
 import os
@@ -14,6 +15,7 @@ import pytest
 import torch
 
 import maxk_kernels as mk
+import scan
 import subgraph as sg
 import transpose as tr
 from arena import POISONS, arena
@@ -47,8 +49,9 @@ def same(got, want, what):
 
 
 def compiled():
+    """The maxk_tr:: fixture and the maxk_scan:: kernels a call launches."""
     with open(FIXTURE) as f:
-        return {ln.strip() for ln in f if ln.strip()}
+        return {ln.strip() for ln in f if ln.strip()} | set(tr.SCAN_KERNELS)
 
 
 def run_case(ptr, idx, nc, dev, what, idx_d=None):
@@ -345,10 +348,34 @@ def test_backwards_on_the_kernels_structure_equal_the_torch_paths(gpu, counted, 
     COVERED.update(tr.kernels(g._num_cols(), consumer == "dense"))
 
 
-# ------------------------------------------------------------------ 5. closure (keep last)
+# ------------------------------------------------------------------ 5. scan lengths
+@pytest.mark.parametrize("n", scan.LENGTHS)
+def test_out_ptr_scan_of_n_items(gpu, n):
+    """out_ptr is scanned over num_cols + 1 = n items, on about 3,000 edges that name the first
+    and the last column. One item means no column, which admits no edge and so no scan: that
+    length is run on the tile histograms instead (one column: one tile of one digit)."""
+    if n == 1:
+        ptr, idx, nc = tr.random_csr(150, 1, 3000, 5)
+        assert (-(-idx.size // tr.TILE)) << tr.digit_bits(nc)[0] == 1
+    else:
+        ptr, idx, nc = tr.plan_case(n - 1)
+    run_case(ptr, idx, nc, gpu, f"out_ptr of {n} items")
+
+
+def test_histogram_scan_carries_into_a_second_round(gpu):
+    """257 tiles of edges under one 11-bit digit: the tile histograms are 257 scan tiles long,
+    one more than a round of the scan's middle step takes."""
+    nc, e = 2 ** tr.MAX_DIGIT_BITS, scan.ROUND * tr.TILE + 1
+    assert tr.digit_bits(nc) == (tr.MAX_DIGIT_BITS,)
+    assert scan.tiles((-(-e // tr.TILE)) << tr.MAX_DIGIT_BITS) == scan.ROUND + 1
+    ptr, idx, _ = tr.random_csr(300, nc, e, 6)
+    run_case(ptr, idx, nc, gpu, "257 tiles of an 11-bit digit")
+
+
+# ------------------------------------------------------------------ 6. closure (keep last)
 def test_every_transpose_instantiation_was_launched_by_a_passing_case(gpu):
     names = compiled()
-    assert len(names) == 12
+    assert len(names) == 9 + len(tr.SCAN_KERNELS) == 12
     missing = sorted(names - COVERED)
     assert not missing, f"instantiations without a passing case: {missing}"
     assert not COVERED - names

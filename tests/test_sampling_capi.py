@@ -260,8 +260,9 @@ def test_restated_names_cover_the_fixture():
     names = kernel_list.read_list(FIXTURE)
     assert names == sorted(set(names)) and all(n.startswith("maxk_sp::") for n in names)
     restated = set(sp.KERNELS) | {sp.sample_kernel_name(f) for f in (-1, 1, 10, 2 ** 31 - 1)}
-    assert restated == set(names) and len(names) == 10
-    assert set(sp.SAMPLER_KERNELS) | set(sp.COMPACT_KERNELS) == set(sp.KERNELS)
+    assert restated == set(names) and len(names) == 7
+    assert set(sp.SAMPLER_KERNELS) | set(sp.COMPACT_KERNELS) == set(sp.KERNELS) | set(sp.SCAN_KERNELS)
+    assert all(n.startswith("maxk_scan::") for n in sp.SCAN_KERNELS)
 
 
 def test_fixture_equals_the_library():

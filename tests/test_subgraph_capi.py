@@ -193,6 +193,18 @@ def test_multigraph_rows_repeated_and_stray_nodes():
     assert sg.subgraph_ref(ptr, idx, [], 4)[0].tolist() == [0]
 
 
+def test_the_loop_free_count_equals_the_restatement():
+    ptr, idx, n = sg.graph()
+    for name in sorted(sg.node_sets()):
+        want = sg.reference(name)
+        got = sg.count_ref(ptr, idx, sg.node_sets()[name], n)
+        assert np.array_equal(got[0], want[0]) and got[0].dtype == np.int32 and got[1] == want[3]
+    for nodes in ([30, 40, 30, sg.HUB, 50, 40, 580], [30, n, -3, sg.HUB, 50, 2 ** 31 - 1, -2 ** 31]):
+        want = sg.subgraph_ref(ptr, idx, nodes, n)
+        got = sg.count_ref(ptr, idx, nodes, n)
+        assert np.array_equal(got[0], want[0]) and got[1] == want[3], nodes
+
+
 def test_node_sets_hold_the_preconditions_of_the_gpu_cases():
     """Selected rows of length 0, 1 and limit - 1 / at / + 1 of every limit the library reports,
     a hub; nothing, some and all of a row kept in each of the three regimes."""
@@ -414,7 +426,8 @@ def test_subgraph_invariants():
 def test_restated_names_cover_the_fixture():
     names = kernel_list.read_list(FIXTURE)
     assert names == sorted(set(names)) and all(n.startswith("maxk_sg::") for n in names)
-    assert set(sg.KERNELS) == set(names) and len(names) == 7
+    assert set(sg.KERNELS) == set(names) | set(sg.SCAN_KERNELS) and len(names) == 4
+    assert all(n.startswith("maxk_scan::") for n in sg.SCAN_KERNELS)
     assert set(sg.COUNT_KERNELS) | set(sg.FILL_KERNELS) == set(sg.KERNELS)
 
 

@@ -276,10 +276,12 @@ def test_cpu_tensors_keep_the_torch_path(name, monkeypatch):
 def test_restated_names_cover_the_fixture():
     names = kernel_list.read_list(FIXTURE)
     assert names == sorted(set(names)) and all(n.startswith("maxk_tr::") for n in names)
-    assert set(names) == tr.pass_kernel_names() | set(tr.SCAN_KERNELS) and len(names) == 12
+    own = set(tr.COMMON_KERNELS) - set(tr.SCAN_KERNELS)
+    assert set(names) == tr.pass_kernel_names() | own and len(names) == 9
+    assert all(n.startswith("maxk_scan::") for n in tr.SCAN_KERNELS)
     for nc in (1, 5000, 2 ** 22 + 1):
         for v in (False, True):
-            assert tr.kernels(nc, v) <= set(names)
+            assert tr.kernels(nc, v) <= set(names) | set(tr.SCAN_KERNELS)
 
 
 def test_fixture_equals_the_library():
@@ -295,5 +297,5 @@ def test_variant_check_names_the_fixtures_pass_kernels():
     run = subprocess.run([CHECK, "transpose"], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                          text=True)
     assert run.returncode == 0, run.stderr
-    want = [n for n in kernel_list.read_list(FIXTURE) if n not in tr.SCAN_KERNELS]
+    want = [n for n in kernel_list.read_list(FIXTURE) if n not in tr.COMMON_KERNELS]
     assert run.stdout.splitlines() == want and set(want) == tr.pass_kernel_names()

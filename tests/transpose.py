@@ -9,6 +9,7 @@ import numpy as np
 
 import gat_heads as gh
 import sampling as sp
+import scan
 
 # csrc/variants_transpose.h, asserted against the header's text by tests/test_transpose_capi.py
 WAVE = 64                 # kTrWave: items a wave ranks at a time
@@ -16,17 +17,16 @@ SUB_RUN = 2048            # kTrSubRun: consecutive items of one wave
 TILE = 8192               # kTrTile: items of a work-group
 MAX_DIGIT_BITS = 11       # kTrMaxDigitBits
 MAX_PASSES = 3            # kTrMaxPasses
-SCAN_TILE = 2048          # kTrScanTile
+SCAN_TILE = scan.TILE     # items of a scan tile (csrc/scan.h)
 HEADER_CONSTANTS = {"kTrWave": WAVE, "kTrSubRun": SUB_RUN, "kTrTile": TILE,
-                    "kTrMaxDigitBits": MAX_DIGIT_BITS, "kTrMaxPasses": MAX_PASSES,
-                    "kTrScanTile": SCAN_TILE}
+                    "kTrMaxDigitBits": MAX_DIGIT_BITS, "kTrMaxPasses": MAX_PASSES}
 SIZES = (WAVE, SUB_RUN, TILE)     # E at each of these - 1, at, + 1
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 VARIANTS = os.path.join(ROOT, "spgemm-gnn_amd", "csrc", "variants_transpose.h")
 
-SCAN_KERNELS = ("maxk_tr::scan_apply_kernel", "maxk_tr::scan_partials_kernel",
-                "maxk_tr::scan_tile_sums_kernel", "maxk_tr::zero_kernel")   # and the one fill
+SCAN_KERNELS = scan.PLAIN_KERNELS                          # both scans are the plain one
+COMMON_KERNELS = SCAN_KERNELS + ("maxk_tr::zero_kernel",)  # and the one fill: in every call
 FIRST, MIDDLE, LAST, ONLY = 0, 1, 2, 3
 
 
@@ -76,9 +76,9 @@ def scratch_bytes(num_rows, num_cols, num_edges):
 
 
 def kernels(num_cols, has_val):
-    """The maxk_tr:: kernels one call with edges launches."""
+    """The maxk_tr:: and maxk_scan:: kernels one call with edges launches."""
     p = len(digit_bits(num_cols))
-    names = set(SCAN_KERNELS) | {"maxk_tr::tile_hist_kernel<true>"}
+    names = set(COMMON_KERNELS) | {"maxk_tr::tile_hist_kernel<true>"}
     if p > 1:
         names.add("maxk_tr::tile_hist_kernel<false>")
     v = "true" if has_val else "false"
@@ -92,7 +92,7 @@ def pass_kernel_names():
     names = set()
     for nc in (1, 2 ** MAX_DIGIT_BITS + 1, 2 ** (2 * MAX_DIGIT_BITS) + 1):
         for v in (False, True):
-            names |= kernels(nc, v) - set(SCAN_KERNELS)
+            names |= kernels(nc, v) - set(COMMON_KERNELS)
     return names
 
 

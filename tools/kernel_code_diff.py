@@ -5,7 +5,8 @@
 
 Every spgemm-gnn_amd/csrc/*.hip of each tree is compiled with the Makefile's FLAGS plus
 --offload-device-only -c, the hipv4-amdgcn-amd-amdhsa--gfx950 object is unbundled and
-disassembled (llvm-objdump -d --no-show-raw-insn, addresses and trailing // comments dropped) and
+disassembled (llvm-objdump -d --no-show-raw-insn; addresses, trailing // comments and the s_nop
+padding behind a function dropped, which is longest behind whichever function comes last) and
 keyed by function name; llvm-readelf --notes gives each kernel's register counts, LDS, scratch and
 kernarg sizes. Prints the names whose instruction lists or resources differ, or that only one
 tree has, and exits non-zero if there are any. The order of emission in the object is not
@@ -48,6 +49,9 @@ def functions(obj):
             cur = out.setdefault(m.group(1), [])
         elif cur is not None and ln.strip() not in ("", "..."):  # "...": padding between functions
             cur.append(re.sub(r"\s*//.*$", "", ln).strip())
+    for body in out.values():  # alignment padding behind a function: longest behind the last one
+        while body and body[-1] == "s_nop 0":
+            body.pop()
     return out
 
 
