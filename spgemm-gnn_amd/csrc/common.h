@@ -175,6 +175,21 @@ __device__ __forceinline__ void clamped_segment(const int32_t* __restrict__ ptr,
   }
 }
 
+// Segment [b, b + n) of row `row` of ptr, clamped into [0, E] so that a ptr that breaks the
+// documented preconditions still indexes inside the arrays; n = 0 past num_rows.
+__device__ __forceinline__ void row_segment(const int32_t* __restrict__ ptr, int64_t row,
+                                            int32_t num_rows, int64_t E, int64_t& b, int32_t& n) {
+  b = 0;
+  n = 0;
+  if (row < num_rows) {
+    int64_t lo = ptr[row], hi = ptr[row + 1];
+    lo = lo < 0 ? 0 : (lo > E ? E : lo);
+    hi = hi < lo ? lo : (hi > E ? E : hi);
+    b = lo;
+    n = (int32_t)(hi - lo);
+  }
+}
+
 // Forward work item: a run of whole destination rows [row0, row0+nrows) (or, nrows < 0, one
 // segment of a long row whose partial sum is added atomically into a row pre-zeroed by
 // zero_rows), with edge range [e0, e1) of the plan's permuted edge order (the task's CSR

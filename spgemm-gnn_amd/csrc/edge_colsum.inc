@@ -9,7 +9,7 @@
   int64_t b;
   int32_t n;
   const int64_t col = col0 + wave * kEsWaveRows + lane / kEsGroup;
-  es_segment(ptr_t, col, num_cols, E, b, n);
+  row_segment(ptr_t, col, num_cols, E, b, n);
   const int32_t ns = n <= kEsShortMax ? n : 0;
   float s = 0.f;
   if (__ballot(ns > 0) != 0) {
@@ -30,7 +30,7 @@
   for (int r = 0; r < kEsTileRows; ++r) {
     int64_t bh;
     int32_t nh;
-    es_segment(ptr_t, col0 + r, num_cols, E, bh, nh);
+    row_segment(ptr_t, col0 + r, num_cols, E, bh, nh);
     if (nh <= kEsMediumMax) continue;
     const GatPermuted src{order + bh, values, edge_hi};
     float a = 0.f;

@@ -41,21 +41,6 @@ __device__ __forceinline__ float es_sum(float v) {
   return v;
 }
 
-// Segment [b, b + n) of a row, clamped into [0, E] so that a ptr that breaks the documented
-// preconditions still indexes inside the arrays.
-__device__ __forceinline__ void es_segment(const int32_t* __restrict__ ptr, int64_t row,
-                                           int32_t num_rows, int64_t E, int64_t& b, int32_t& n) {
-  b = 0;
-  n = 0;
-  if (row < num_rows) {
-    int64_t lo = ptr[row], hi = ptr[row + 1];
-    lo = lo < 0 ? 0 : (lo > E ? E : lo);
-    hi = hi < lo ? lo : (hi > E ? E : hi);
-    b = lo;
-    n = (int32_t)(hi - lo);
-  }
-}
-
 // Element j of a row that is an array.
 struct EsArray {
   const float* __restrict__ x;

@@ -46,7 +46,7 @@ __global__ __launch_bounds__(kEsThreads) void edge_softmax_fwd_kernel(
   // the wave's own rows: short ones side by side, medium ones one after the other
   int64_t b;
   int32_t n;
-  es_segment(ptr, row0 + wave * kEsWaveRows + lane / kEsGroup, num_rows, E, b, n);
+  row_segment(ptr, row0 + wave * kEsWaveRows + lane / kEsGroup, num_rows, E, b, n);
   const int32_t ns = n <= kEsShortMax ? n : 0;
   if (__ballot(ns > 0) != 0) {
     // a group with no short row reads element 0 (E > 0) and writes nothing
@@ -65,7 +65,7 @@ __global__ __launch_bounds__(kEsThreads) void edge_softmax_fwd_kernel(
   for (int r = 0; r < kEsTileRows; ++r) {
     int64_t bh;
     int32_t nh;
-    es_segment(ptr, row0 + r, num_rows, E, bh, nh);
+    row_segment(ptr, row0 + r, num_rows, E, bh, nh);
     if (nh <= kEsMediumMax) continue;
     es_fwd_hub(EsArray{logits + bh}, out + bh, nh, tid, lane, wave, red);
   }
@@ -82,7 +82,7 @@ __global__ __launch_bounds__(kEsThreads) void edge_softmax_bwd_kernel(
 
   int64_t b;
   int32_t n;
-  es_segment(ptr, row0 + wave * kEsWaveRows + lane / kEsGroup, num_rows, E, b, n);
+  row_segment(ptr, row0 + wave * kEsWaveRows + lane / kEsGroup, num_rows, E, b, n);
   const int32_t ns = n <= kEsShortMax ? n : 0;
   if (__ballot(ns > 0) != 0) {
     const int64_t bs = ns > 0 ? b : 0;
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(kEsThreads) void edge_softmax_bwd_kernel(
   for (int r = 0; r < kEsTileRows; ++r) {
     int64_t bh;
     int32_t nh;
-    es_segment(ptr, row0 + r, num_rows, E, bh, nh);
+    row_segment(ptr, row0 + r, num_rows, E, bh, nh);
     if (nh <= kEsMediumMax) continue;
     es_bwd_hub(y + bh, gy + bh, out + bh, nh, tid, lane, wave, red, EsNoPost{});
     __syncthreads();  // red is free for the tile's next hub

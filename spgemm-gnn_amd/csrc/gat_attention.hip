@@ -32,7 +32,7 @@
 namespace maxk {
 
 // Element j of a row's scores: idx at the row's segment, el [num_cols], er_r the row's own score.
-// idx is clamped into [0, num_cols) before use, as es_segment clamps ptr.
+// idx is clamped into [0, num_cols) before use, as row_segment clamps ptr.
 struct GatScore {
   const int32_t* __restrict__ idx;
   const float* __restrict__ el;

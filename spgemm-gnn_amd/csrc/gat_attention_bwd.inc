@@ -10,7 +10,7 @@
   int64_t b;
   int32_t n;
   const int64_t row = row0 + wave * kEsWaveRows + lane / kEsGroup;
-  es_segment(ptr, row, num_rows, E, b, n);
+  row_segment(ptr, row, num_rows, E, b, n);
   const int32_t ns = n <= kEsShortMax ? n : 0;
   float s = 0.f;
   if (__ballot(ns > 0) != 0) {
@@ -34,7 +34,7 @@
   for (int r = 0; r < kEsTileRows; ++r) {
     int64_t bh;
     int32_t nh;
-    es_segment(ptr, row0 + r, num_rows, E, bh, nh);
+    row_segment(ptr, row0 + r, num_rows, E, bh, nh);
     if (nh <= kEsMediumMax) continue;
     const GatScore post{idx + bh, el, er[row0 + r], slope, col_hi};
     const float acc = es_bwd_hub(y + bh, gy + bh, out + bh, nh, tid, lane, wave, red, post);

@@ -7,13 +7,8 @@
 //              with e = order[j], r = idx_t[j], s = sp_index[c, l]
 //
 // No plan, no scratch, no global atomics: both kernels read the plain [num_cols, k] tables and the
-// CSR (forward) or the transposed structure (backward) as they are.
-//
-// An edge is served by LP adjacent lanes (a lane group), LP = k rounded up to a power of two in
-// [8, 64]; lane `sub` of the group holds slot sub (and sub + 64, ... above k = 64). A work-group
-// of 4 waves owns a tile of 16 rows (columns) and serves each by its length, as the edge softmax
-// does: at most kHeadsShortMax edges by one lane group, at most kHeadsMediumMax by one wave whose
-// 64 / LP groups take the edges j = g, g + G, ..., a longer one by the whole work-group. Edges of a
+// CSR (forward) or the transposed structure (backward) as they are. Lane groups, the tile and its
+// three passes, and the backward's combination of the groups' sums are lane_groups.h. Edges of a
 // group are taken in order, the groups' partial sums are combined by a balanced tree in a fixed
 // order, so a row's bits depend on its own inputs and its length alone.
 //
@@ -31,30 +26,10 @@ namespace maxk_mh {
 
 using maxk::check_ranges;
 using maxk::clampi;
+using maxk::kWave;
 using maxk::Range;
 using maxk::set_error;
-
-// Segment [b, b + n) of row `row` of ptr, clamped into [0, E]; n = 0 past num_rows.
-__device__ __forceinline__ void segment(const int32_t* __restrict__ ptr, int64_t row,
-                                        int32_t num_rows, int64_t E, int64_t& b, int32_t& n) {
-  b = 0;
-  n = 0;
-  if (row < num_rows) {
-    int64_t lo = ptr[row], hi = ptr[row + 1];
-    lo = lo < 0 ? 0 : (lo > E ? E : lo);
-    hi = hi < lo ? lo : (hi > E ? E : hi);
-    b = lo;
-    n = (int32_t)(hi - lo);
-  }
-}
-
-// LDS accesses of one wave are executed in program order; this keeps the compiler from moving
-// them across the point where lanes read what other lanes of the wave wrote.
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+using maxk::lg::wave_lds_sync;
 
 __device__ __forceinline__ void lds_add(float* p, float v) {
   __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);  // ds_add_f32
@@ -125,58 +100,42 @@ __device__ __forceinline__ void fwd_edges(const FwdArgs& a, float* acc, int64_t 
 }
 
 template <int LP>
-__global__ __launch_bounds__(kHeadsThreads) void heads_fwd_kernel(const FwdArgs a) {
+__global__ __launch_bounds__(lg::kThreads) void heads_fwd_kernel(const FwdArgs a) {
   extern __shared__ float lds[];  // NG accumulator rows of D + 1 floats
-  constexpr int G = kHeadsWave / LP;   // lane groups of a wave
-  constexpr int NG = kHeadsWaves * G;  // of the work-group
-  const int tid = threadIdx.x;
-  const int lane = tid & (kHeadsWave - 1), wave = tid / kHeadsWave;
-  const int g = lane / LP, sub = lane % LP, gid = wave * G + g;
+  const lg::Place<LP> p{};
+  constexpr int G = p.G, NG = p.NG;
   const int D = a.D, stride = a.D + 1;
-  float* mine = lds + gid * stride;
-  float* wacc = lds + wave * G * stride;
-  const int64_t row0 = (int64_t)blockIdx.x * kHeadsTile;
-  int64_t b;
-  int32_t n;
+  float* mine = lds + p.gid * stride;
+  float* wacc = lds + p.wave * G * stride;
+  const int64_t row0 = (int64_t)blockIdx.x * lg::kTile;
 
-  // short rows (and empty ones): one lane group each, its edges in order
-  for (int t = gid; t < kHeadsTile; t += NG) {
-    const int64_t row = row0 + t;
-    segment(a.ptr, row, a.num_rows, a.E, b, n);
-    if (row >= a.num_rows || n > kHeadsShortMax) continue;
-    for (int j = sub; j < D; j += LP) mine[j] = 0.f;
+  // its edges in order
+  lg::short_rows(p, a.ptr, row0, a.num_rows, a.E, [&](int64_t row, int64_t b, int32_t n) {
+    for (int j = p.sub; j < D; j += LP) mine[j] = 0.f;
     wave_lds_sync();
-    fwd_edges<LP>(a, mine, b, n, 0, 1, sub);
+    fwd_edges<LP>(a, mine, b, n, 0, 1, p.sub);
     wave_lds_sync();
-    for (int j = sub; j < D; j += LP) a.out[row * D + j] = mine[j];
+    for (int j = p.sub; j < D; j += LP) a.out[row * D + j] = mine[j];
     wave_lds_sync();
-  }
+  });
 
-  // medium rows: one wave each (wave-uniform branch)
-  for (int t = wave; t < kHeadsTile; t += kHeadsWaves) {
-    const int64_t row = row0 + t;
-    segment(a.ptr, row, a.num_rows, a.E, b, n);
-    if (n <= kHeadsShortMax || n > kHeadsMediumMax) continue;
-    for (int j = lane; j < G * stride; j += kHeadsWave) wacc[j] = 0.f;
+  lg::medium_rows(p, a.ptr, row0, a.num_rows, a.E, [&](int64_t row, int64_t b, int32_t n) {
+    for (int j = p.lane; j < G * stride; j += kWave) wacc[j] = 0.f;
     wave_lds_sync();
-    fwd_edges<LP>(a, mine, b, n, g, G, sub);
+    fwd_edges<LP>(a, mine, b, n, p.g, G, p.sub);
     wave_lds_sync();
-    for (int j = lane; j < D; j += kHeadsWave) a.out[row * D + j] = tree<G>(wacc + j, stride);
+    for (int j = p.lane; j < D; j += kWave) a.out[row * D + j] = tree<G>(wacc + j, stride);
     wave_lds_sync();
-  }
+  });
 
-  // hub rows: the whole work-group (block-uniform branch)
-  for (int t = 0; t < kHeadsTile; ++t) {
-    const int64_t row = row0 + t;
-    segment(a.ptr, row, a.num_rows, a.E, b, n);
-    if (n <= kHeadsMediumMax) continue;
+  lg::hub_rows(a.ptr, row0, a.num_rows, a.E, [&](int64_t row, int64_t b, int32_t n) {
     __syncthreads();  // every wave is done with its accumulators
-    for (int j = tid; j < NG * stride; j += kHeadsThreads) lds[j] = 0.f;
+    for (int j = p.tid; j < NG * stride; j += lg::kThreads) lds[j] = 0.f;
     __syncthreads();
-    fwd_edges<LP>(a, mine, b, n, gid, NG, sub);
+    fwd_edges<LP>(a, mine, b, n, p.gid, NG, p.sub);
     __syncthreads();
-    for (int j = tid; j < D; j += kHeadsThreads) a.out[row * D + j] = tree<NG>(lds + j, stride);
-  }
+    for (int j = p.tid; j < D; j += lg::kThreads) a.out[row * D + j] = tree<NG>(lds + j, stride);
+  });
 }
 
 // --------------------------------------------------------------------------------- backward
@@ -287,12 +246,12 @@ __device__ __forceinline__ void bwd_edges(const BwdArgs& a, int64_t c, int64_t b
           for (int q = 0; q < half; ++q) {
             const float send = up ? v[q] : v[q + half];
             const float keep = up ? v[q + half] : v[q];
-            v[q] = keep + __shfl_xor(send, 1 << t, kHeadsWave);
+            v[q] = keep + __shfl_xor(send, 1 << t, kWave);
           }
         }
         float tot = v[0];
 #pragma unroll
-        for (int m = HP; m < LP; m <<= 1) tot = tot + __shfl_xor(tot, m, kHeadsWave);
+        for (int m = HP; m < LP; m <<= 1) tot = tot + __shfl_xor(tot, m, kWave);
         if (writer && ok[u]) a.grad_alpha[(int64_t)mine * a.E + e[u]] = tot;
       }
     }
@@ -300,101 +259,52 @@ __device__ __forceinline__ void bwd_edges(const BwdArgs& a, int64_t c, int64_t b
 }
 
 template <int LP, int HP>
-__global__ __launch_bounds__(kHeadsThreads) void heads_bwd_kernel(const BwdArgs a) {
+__global__ __launch_bounds__(lg::kThreads) void heads_bwd_kernel(const BwdArgs a) {
   static_assert(LP >= HP, "the reduce-scatter ends with one head per lane");
-  constexpr int S = LP == kHeadsWave ? maxk::kMaxDim / kHeadsWave : 1;  // slots of a lane
-  constexpr int G = kHeadsWave / LP;
-  constexpr int NG = kHeadsWaves * G;
-  __shared__ float red[kHeadsWaves][maxk::kMaxDim];
-  const int tid = threadIdx.x;
-  const int lane = tid & (kHeadsWave - 1), wave = tid / kHeadsWave;
-  const int g = lane / LP, sub = lane % LP, gid = wave * G + g;
+  constexpr int S = lg::lane_slots(LP);
+  __shared__ float red[lg::kWaves][maxk::kMaxDim];
+  const lg::Place<LP> p{};
   const int k = a.k;
-  const int64_t col0 = (int64_t)blockIdx.x * kHeadsTile;
-  int64_t b;
-  int32_t n;
-  float gsp[S];
+  const int64_t col0 = (int64_t)blockIdx.x * lg::kTile;
 
-  // short columns (and empty ones): one lane group each
-  for (int t = gid; t < kHeadsTile; t += NG) {
-    const int64_t col = col0 + t;
-    segment(a.ptr_t, col, a.num_cols, a.E, b, n);
-    if (col >= a.num_cols || n > kHeadsShortMax) continue;
-#pragma unroll
-    for (int i = 0; i < S; ++i) gsp[i] = 0.f;
-    bwd_edges<LP, HP, S>(a, col, b, n, 0, 1, sub, gsp);
-    if (a.grad_sp) {
-#pragma unroll
-      for (int i = 0; i < S; ++i)
-        if (sub + LP * i < k) a.grad_sp[col * k + sub + LP * i] = gsp[i];
-    }
-  }
+  // grad_sp may be null: then the passes are there for grad_alpha, which bwd_edges stores
+  lg::short_rows(p, a.ptr_t, col0, a.num_cols, a.E, [&](int64_t col, int64_t b, int32_t n) {
+    float gsp[S] = {};
+    bwd_edges<LP, HP, S>(a, col, b, n, 0, 1, p.sub, gsp);
+    if (a.grad_sp) lg::store_group(p, gsp, k, a.grad_sp, col);
+  });
 
-  // medium columns: one wave each (wave-uniform branch), groups combined by a butterfly
-  for (int t = wave; t < kHeadsTile; t += kHeadsWaves) {
-    const int64_t col = col0 + t;
-    segment(a.ptr_t, col, a.num_cols, a.E, b, n);
-    if (n <= kHeadsShortMax || n > kHeadsMediumMax) continue;
-#pragma unroll
-    for (int i = 0; i < S; ++i) gsp[i] = 0.f;
-    bwd_edges<LP, HP, S>(a, col, b, n, g, G, sub, gsp);
-    if (a.grad_sp) {
-#pragma unroll
-      for (int i = 0; i < S; ++i) {
-#pragma unroll
-        for (int m = LP; m < kHeadsWave; m <<= 1) gsp[i] = gsp[i] + __shfl_xor(gsp[i], m, kHeadsWave);
-        if (g == 0 && sub + LP * i < k) a.grad_sp[col * k + sub + LP * i] = gsp[i];
-      }
-    }
-  }
+  lg::medium_rows(p, a.ptr_t, col0, a.num_cols, a.E, [&](int64_t col, int64_t b, int32_t n) {
+    float gsp[S] = {};
+    bwd_edges<LP, HP, S>(a, col, b, n, p.g, p.G, p.sub, gsp);
+    if (a.grad_sp) lg::reduce_wave_and_store(p, gsp, k, a.grad_sp, col);
+  });
 
-  // hub columns: the whole work-group (block-uniform branch), waves as (w0 + w1) + (w2 + w3)
-  for (int t = 0; t < kHeadsTile; ++t) {
-    const int64_t col = col0 + t;
-    segment(a.ptr_t, col, a.num_cols, a.E, b, n);
-    if (n <= kHeadsMediumMax) continue;
-#pragma unroll
-    for (int i = 0; i < S; ++i) gsp[i] = 0.f;
-    bwd_edges<LP, HP, S>(a, col, b, n, gid, NG, sub, gsp);
-    if (a.grad_sp) {
-      __syncthreads();  // red is free (the tile's previous hub was read)
-#pragma unroll
-      for (int i = 0; i < S; ++i) {
-#pragma unroll
-        for (int m = LP; m < kHeadsWave; m <<= 1) gsp[i] = gsp[i] + __shfl_xor(gsp[i], m, kHeadsWave);
-        if (g == 0 && sub + LP * i < k) red[wave][sub + LP * i] = gsp[i];
-      }
-      __syncthreads();
-      for (int l = tid; l < k; l += kHeadsThreads)
-        a.grad_sp[col * k + l] = (red[0][l] + red[1][l]) + (red[2][l] + red[3][l]);
-    }
-  }
+  lg::hub_rows(a.ptr_t, col0, a.num_cols, a.E, [&](int64_t col, int64_t b, int32_t n) {
+    float gsp[S] = {};
+    bwd_edges<LP, HP, S>(a, col, b, n, p.gid, p.NG, p.sub, gsp);
+    if (a.grad_sp) lg::reduce_block_and_store(p, gsp, k, a.grad_sp, col, red);
+  });
 }
 
 // ------------------------------------------------------------------------------ entry points
 // sizes, k, heads and strides shared by both calls; strides are resolved (0: the row width)
 static int check_shape(const std::string& w, int32_t H, int32_t num_rows, int32_t num_cols,
                        int64_t E, int32_t D, int32_t k, int64_t& ds, int64_t& is) {
-  MAXK_CHECK_ARG(num_rows >= 0 && num_cols >= 0 && E >= 0 && E <= (int64_t)INT32_MAX,
-                 w + "sizes out of range");
-  MAXK_CHECK_ARG(D >= 1 && D <= maxk::kMaxDim, w + "dim_origin must be in [1, 256]");
-  MAXK_CHECK_ARG(k >= 1 && k <= D, w + "k must be between 1 and input dimension");
-  MAXK_CHECK_ARG(H >= 1 && D % H == 0, w + "num_heads must be >= 1 and divide dim_origin");
-  if ((D / H) % 4 != 0) {
-    set_error(w + "dim_origin / num_heads must be a multiple of 4");
-    return MAXK_ERR_UNSUPPORTED;
-  }
-  if (H > kHeadsMaxHeads) {
-    set_error(w + "num_heads above 16 is not supported");
-    return MAXK_ERR_UNSUPPORTED;
-  }
-  if (ds == 0) ds = k;
-  if (is == 0) is = k;
-  MAXK_CHECK_ARG(ds >= k, w + "data_stride must be >= k (0: k)");
-  MAXK_CHECK_ARG(is >= k, w + "index_stride must be >= k (0: k)");
-  MAXK_CHECK_ARG(E == 0 || num_cols > 0, w + "sizes out of range: edges without columns");
-  MAXK_CHECK_ARG(E == 0 || num_rows > 0, w + "sizes out of range: edges without rows");
-  return MAXK_OK;
+  return lg::check_shape(w, num_rows, num_cols, E, D, k, is, [&]() -> int {
+    MAXK_CHECK_ARG(H >= 1 && D % H == 0, w + "num_heads must be >= 1 and divide dim_origin");
+    if ((D / H) % 4 != 0) {
+      set_error(w + "dim_origin / num_heads must be a multiple of 4");
+      return MAXK_ERR_UNSUPPORTED;
+    }
+    if (H > kHeadsMaxHeads) {
+      set_error(w + "num_heads above 16 is not supported");
+      return MAXK_ERR_UNSUPPORTED;
+    }
+    if (ds == 0) ds = k;
+    MAXK_CHECK_ARG(ds >= k, w + "data_stride must be >= k (0: k)");
+    return MAXK_OK;
+  });
 }
 
 static int forward_impl(const int32_t* ptr, const int32_t* idx, const float* alpha,
@@ -420,12 +330,11 @@ static int forward_impl(const int32_t* ptr, const int32_t* idx, const float* alp
   if (rc != MAXK_OK) return rc;
   const FwdArgs a{ptr, idx, alpha, sp_data, ds, sp_index, is, out, N, NC, E, D, k,
                   heads_magic(D / H)};
-  const dim3 grid((unsigned)(((int64_t)N + kHeadsTile - 1) / kHeadsTile));
   if (int e = maxk::dispatch_variant(
           kHeadsFwdVariants, select_heads_fwd_variant(k), [&](auto i) -> int {
             constexpr int LP = kHeadsFwdVariants[decltype(i)::value].lp;
-            const size_t lds = sizeof(float) * (size_t)(kHeadsThreads / LP) * (size_t)(D + 1);
-            hipLaunchKernelGGL(heads_fwd_kernel<LP>, grid, dim3(kHeadsThreads), lds,
+            const size_t lds = sizeof(float) * (size_t)(lg::kThreads / LP) * (size_t)(D + 1);
+            hipLaunchKernelGGL(heads_fwd_kernel<LP>, lg::tile_grid(N), dim3(lg::kThreads), lds,
                                (hipStream_t)stream, a);
             return MAXK_OK;
           }))
@@ -465,12 +374,11 @@ static int backward_impl(const int32_t* ptr_t, const int32_t* idx_t, const int32
   if (rc != MAXK_OK) return rc;
   const BwdArgs a{ptr_t, idx_t, order, alpha, grad_out, gs, sp_data, ds, sp_index, is, grad_sp,
                   grad_alpha, H, N, NC, E, D, k, heads_magic(D / H)};
-  const dim3 grid((unsigned)(((int64_t)NC + kHeadsTile - 1) / kHeadsTile));
   if (int e = maxk::dispatch_variant(
           kHeadsBwdVariants, select_heads_bwd_variant(k, H), [&](auto i) -> int {
             constexpr HeadsBwdVariant v = kHeadsBwdVariants[decltype(i)::value];
-            hipLaunchKernelGGL((heads_bwd_kernel<v.lp, v.hp>), grid, dim3(kHeadsThreads), 0,
-                               (hipStream_t)stream, a);
+            hipLaunchKernelGGL((heads_bwd_kernel<v.lp, v.hp>), lg::tile_grid(NC),
+                               dim3(lg::kThreads), 0, (hipStream_t)stream, a);
             return MAXK_OK;
           }))
     return e;
@@ -504,6 +412,7 @@ extern "C" int maxk_heads_aggregate_backward(
 }
 
 extern "C" int maxk_heads_row_limits(int32_t* out, int32_t capacity) {
-  return maxk::copy_limits(out, capacity, {maxk_mh::kHeadsShortMax, maxk_mh::kHeadsMediumMax,
-                                            maxk_mh::kHeadsShortMax, maxk_mh::kHeadsMediumMax});
+  namespace lg = maxk::lg;
+  return maxk::copy_limits(out, capacity,
+                           {lg::kShortMax, lg::kMediumMax, lg::kShortMax, lg::kMediumMax});
 }

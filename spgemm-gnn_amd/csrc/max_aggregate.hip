@@ -7,11 +7,8 @@
 //                              * grad_out[r, s]      with e = order[j], r = idx_t[j],
 //                                                    s = sp_index[c, l]
 //
-// No plan, no scratch, no global atomics. The shape is that of heads_aggregate.hip: an edge is
-// served by LP adjacent lanes (a lane group), LP = k rounded up to a power of two in [8, 64]; a
-// work-group of 4 waves owns a tile of 16 rows (columns) and serves each by its length: at most
-// kMaxShortMax edges by one lane group, at most kMaxMediumMax by one wave, a longer one by the
-// whole work-group.
+// No plan, no scratch, no global atomics. Lane groups, the tile and its three passes, and the
+// backward's combination of the groups' sums are lane_groups.h, shared with heads_aggregate.hip.
 //
 // Forward: a row's state in LDS is, per feature, a 64-bit cell
 //     order_key(value) << 32 | ~(j * 256 + l)          j: the edge's place in its row, l: the slot
@@ -22,8 +19,7 @@
 // lanes of an edge mark the feature in a 256-bit map of their lane group (ds_or_rtn_b32) and only
 // the first to mark it counts. The implicit zero competes where the count stays below the row's
 // length. Backward: a lane keeps grad_sp of its slot in a register across the column's entries
-// and reads grad_out only where arg_edge / arg_slot name its (edge, slot); groups and waves
-// combine by the fixed balanced tree of the heads backward.
+// and reads grad_out only where arg_edge / arg_slot name its (edge, slot).
 #include "common.h"
 #include "variants_max.h"
 
@@ -31,30 +27,10 @@ namespace maxk_mx {
 
 using maxk::check_ranges;
 using maxk::clampi;
+using maxk::kWave;
 using maxk::Range;
 using maxk::set_error;
-
-// Segment [b, b + n) of row `row` of ptr, clamped into [0, E]; n = 0 past num_rows.
-__device__ __forceinline__ void segment(const int32_t* __restrict__ ptr, int64_t row,
-                                        int32_t num_rows, int64_t E, int64_t& b, int32_t& n) {
-  b = 0;
-  n = 0;
-  if (row < num_rows) {
-    int64_t lo = ptr[row], hi = ptr[row + 1];
-    lo = lo < 0 ? 0 : (lo > E ? E : lo);
-    hi = hi < lo ? lo : (hi > E ? E : hi);
-    b = lo;
-    n = (int32_t)(hi - lo);
-  }
-}
-
-// LDS accesses of one wave are executed in program order; this keeps the compiler from moving
-// them across the point where lanes read what other lanes of the wave wrote.
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+using maxk::lg::wave_lds_sync;
 
 // The order of the exact top-k (maxk_topk.hip, order_key): larger float, larger key; +0 above
 // -0; every NaN is the largest key. No key is 0.
@@ -170,80 +146,67 @@ __device__ __forceinline__ void fwd_emit(const FwdArgs& a, int64_t row, int s, u
 }
 
 template <int LP, bool ARG>
-__global__ __launch_bounds__(kMaxThreads) void max_fwd_kernel(const FwdArgs a) {
+__global__ __launch_bounds__(lg::kThreads) void max_fwd_kernel(const FwdArgs a) {
   extern __shared__ uint64_t lds[];  // R x D cells, R x D counts, NG x U feature maps
-  constexpr int G = kMaxWave / LP;   // lane groups of a wave
-  constexpr int NG = kMaxWaves * G;  // of the work-group
+  const lg::Place<LP> p{};
+  constexpr int G = p.G, NG = p.NG;
   constexpr int R = max_fwd_states(LP);
-  static_assert(R >= kMaxWaves, "a wave has a row state of its own");
-  const int tid = threadIdx.x;
-  const int lane = tid & (kMaxWave - 1), wave = tid / kMaxWave;
-  const int g = lane / LP, sub = lane % LP, gid = wave * G + g;
+  static_assert(R >= lg::kWaves, "a wave has a row state of its own");
   const int D = a.D;
   uint64_t* cells = lds;
   uint32_t* hits = reinterpret_cast<uint32_t*>(cells + R * D);
-  uint32_t* seen = hits + R * D + gid * (kFwdEdgesInFlight * kSeenWords);
-  const int64_t row0 = (int64_t)blockIdx.x * kMaxTile;
-  int64_t b;
-  int32_t n;
+  uint32_t* seen = hits + R * D + p.gid * (kFwdEdgesInFlight * kSeenWords);
+  const int64_t row0 = (int64_t)blockIdx.x * lg::kTile;
 
-  // short rows (and empty ones): one lane group each, with the row state of the group
-  for (int t = gid; t < kMaxTile; t += NG) {
-    const int64_t row = row0 + t;
-    segment(a.ptr, row, a.num_rows, a.E, b, n);
-    if (row >= a.num_rows || n > kMaxShortMax) continue;
-    uint64_t* cell = cells + (gid % R) * D;
-    uint32_t* hit = hits + (gid % R) * D;
+  // with the row state of the group
+  lg::short_rows(p, a.ptr, row0, a.num_rows, a.E, [&](int64_t row, int64_t b, int32_t n) {
+    uint64_t* cell = cells + (p.gid % R) * D;
+    uint32_t* hit = hits + (p.gid % R) * D;
     if (n == 0) {
-      for (int j = sub; j < D; j += LP) fwd_emit<ARG>(a, row, j, 0u, 0u, b, n);
-      continue;
+      for (int j = p.sub; j < D; j += LP) fwd_emit<ARG>(a, row, j, 0u, 0u, b, n);
+      return;
     }
-    for (int j = sub; j < D; j += LP) {
+    for (int j = p.sub; j < D; j += LP) {
       cell[j] = 0u;
       hit[j] = 0u;
     }
     wave_lds_sync();
-    fwd_edges<LP>(a, cell, hit, seen, b, n, 0, 1, sub);
-    for (int j = sub; j < D; j += LP) fwd_emit<ARG>(a, row, j, cell[j], hit[j], b, n);
+    fwd_edges<LP>(a, cell, hit, seen, b, n, 0, 1, p.sub);
+    for (int j = p.sub; j < D; j += LP) fwd_emit<ARG>(a, row, j, cell[j], hit[j], b, n);
     wave_lds_sync();
-  }
+  });
   __syncthreads();  // the row states change hands: group gid's to wave `wave`
 
-  // medium rows: one wave each (wave-uniform branch), its groups on one row state
+  // a wave's groups on one row state
   {
-    uint64_t* cell = cells + wave * D;
-    uint32_t* hit = hits + wave * D;
-    for (int t = wave; t < kMaxTile; t += kMaxWaves) {
-      const int64_t row = row0 + t;
-      segment(a.ptr, row, a.num_rows, a.E, b, n);
-      if (n <= kMaxShortMax || n > kMaxMediumMax) continue;
-      for (int j = lane; j < D; j += kMaxWave) {
+    uint64_t* cell = cells + p.wave * D;
+    uint32_t* hit = hits + p.wave * D;
+    lg::medium_rows(p, a.ptr, row0, a.num_rows, a.E, [&](int64_t row, int64_t b, int32_t n) {
+      for (int j = p.lane; j < D; j += kWave) {
         cell[j] = 0u;
         hit[j] = 0u;
       }
       wave_lds_sync();
-      fwd_edges<LP>(a, cell, hit, seen, b, n, g, G, sub);
+      fwd_edges<LP>(a, cell, hit, seen, b, n, p.g, G, p.sub);
       wave_lds_sync();
-      for (int j = lane; j < D; j += kMaxWave) fwd_emit<ARG>(a, row, j, cell[j], hit[j], b, n);
+      for (int j = p.lane; j < D; j += kWave) fwd_emit<ARG>(a, row, j, cell[j], hit[j], b, n);
       wave_lds_sync();
-    }
+    });
   }
 
-  // hub rows: the whole work-group (block-uniform branch) on row state 0
-  for (int t = 0; t < kMaxTile; ++t) {
-    const int64_t row = row0 + t;
-    segment(a.ptr, row, a.num_rows, a.E, b, n);
-    if (n <= kMaxMediumMax) continue;
+  // on row state 0
+  lg::hub_rows(a.ptr, row0, a.num_rows, a.E, [&](int64_t row, int64_t b, int32_t n) {
     __syncthreads();  // every wave is done with its row state
-    for (int j = tid; j < D; j += kMaxThreads) {
+    for (int j = p.tid; j < D; j += lg::kThreads) {
       cells[j] = 0u;
       hits[j] = 0u;
     }
     __syncthreads();
-    fwd_edges<LP>(a, cells, hits, seen, b, n, gid, NG, sub);
+    fwd_edges<LP>(a, cells, hits, seen, b, n, p.gid, NG, p.sub);
     __syncthreads();
-    for (int j = tid; j < D; j += kMaxThreads) fwd_emit<ARG>(a, row, j, cells[j], hits[j], b, n);
-  }
+    for (int j = p.tid; j < D; j += lg::kThreads)
+      fwd_emit<ARG>(a, row, j, cells[j], hits[j], b, n);
+  });
 }
 
 // --------------------------------------------------------------------------------- backward
@@ -312,92 +275,79 @@ __device__ __forceinline__ void bwd_edges(const BwdArgs& a, int64_t c, int64_t b
   }
 }
 
+// The three passes and the combination of the groups' sums are written out here, not taken from
+// lane_groups.h: through those helpers the compiler orders this kernel's gathers differently, and
+// it measured 1 to 2 % slower in two passes out of two, which is at the edge of what the timing
+// resolves (profiles/lane_groups.md). As written it compiles to the code it always had. A change to short_rows / medium_rows / hub_rows or to the epilogue functions of
+// lane_groups.h has to be made here too.
 template <int LP>
-__global__ __launch_bounds__(kMaxThreads) void max_bwd_kernel(const BwdArgs a) {
-  constexpr int S = LP == kMaxWave ? maxk::kMaxDim / kMaxWave : 1;  // slots of a lane
-  constexpr int G = kMaxWave / LP;
-  constexpr int NG = kMaxWaves * G;
-  __shared__ float red[kMaxWaves][maxk::kMaxDim];
-  const int tid = threadIdx.x;
-  const int lane = tid & (kMaxWave - 1), wave = tid / kMaxWave;
-  const int g = lane / LP, sub = lane % LP, gid = wave * G + g;
+__global__ __launch_bounds__(lg::kThreads) void max_bwd_kernel(const BwdArgs a) {
+  constexpr int S = lg::lane_slots(LP);
+  __shared__ float red[lg::kWaves][maxk::kMaxDim];
+  const lg::Place<LP> p{};
   const int k = a.k;
-  const int64_t col0 = (int64_t)blockIdx.x * kMaxTile;
+  const int64_t col0 = (int64_t)blockIdx.x * lg::kTile;
   int64_t b;
   int32_t n;
   float gsp[S];
 
   // short columns (and empty ones): one lane group each
-  for (int t = gid; t < kMaxTile; t += NG) {
+  for (int t = p.gid; t < lg::kTile; t += p.NG) {
     const int64_t col = col0 + t;
-    segment(a.ptr_t, col, a.num_cols, a.E, b, n);
-    if (col >= a.num_cols || n > kMaxShortMax) continue;
+    maxk::row_segment(a.ptr_t, col, a.num_cols, a.E, b, n);
+    if (col >= a.num_cols || n > lg::kShortMax) continue;
 #pragma unroll
     for (int i = 0; i < S; ++i) gsp[i] = 0.f;
-    bwd_edges<LP, S>(a, col, b, n, 0, 1, sub, gsp);
+    bwd_edges<LP, S>(a, col, b, n, 0, 1, p.sub, gsp);
 #pragma unroll
     for (int i = 0; i < S; ++i)
-      if (sub + LP * i < k) a.grad_sp[col * k + sub + LP * i] = gsp[i];
+      if (p.sub + LP * i < k) a.grad_sp[col * k + p.sub + LP * i] = gsp[i];
   }
 
   // medium columns: one wave each (wave-uniform branch), groups combined by a butterfly
-  for (int t = wave; t < kMaxTile; t += kMaxWaves) {
+  for (int t = p.wave; t < lg::kTile; t += lg::kWaves) {
     const int64_t col = col0 + t;
-    segment(a.ptr_t, col, a.num_cols, a.E, b, n);
-    if (n <= kMaxShortMax || n > kMaxMediumMax) continue;
+    maxk::row_segment(a.ptr_t, col, a.num_cols, a.E, b, n);
+    if (n <= lg::kShortMax || n > lg::kMediumMax) continue;
 #pragma unroll
     for (int i = 0; i < S; ++i) gsp[i] = 0.f;
-    bwd_edges<LP, S>(a, col, b, n, g, G, sub, gsp);
+    bwd_edges<LP, S>(a, col, b, n, p.g, p.G, p.sub, gsp);
 #pragma unroll
     for (int i = 0; i < S; ++i) {
 #pragma unroll
-      for (int m = LP; m < kMaxWave; m <<= 1) gsp[i] = gsp[i] + __shfl_xor(gsp[i], m, kMaxWave);
-      if (g == 0 && sub + LP * i < k) a.grad_sp[col * k + sub + LP * i] = gsp[i];
+      for (int m = LP; m < kWave; m <<= 1) gsp[i] = gsp[i] + __shfl_xor(gsp[i], m, kWave);
+      if (p.g == 0 && p.sub + LP * i < k) a.grad_sp[col * k + p.sub + LP * i] = gsp[i];
     }
   }
 
   // hub columns: the whole work-group (block-uniform branch), waves as (w0 + w1) + (w2 + w3)
-  for (int t = 0; t < kMaxTile; ++t) {
+  for (int t = 0; t < lg::kTile; ++t) {
     const int64_t col = col0 + t;
-    segment(a.ptr_t, col, a.num_cols, a.E, b, n);
-    if (n <= kMaxMediumMax) continue;
+    maxk::row_segment(a.ptr_t, col, a.num_cols, a.E, b, n);
+    if (n <= lg::kMediumMax) continue;
 #pragma unroll
     for (int i = 0; i < S; ++i) gsp[i] = 0.f;
-    bwd_edges<LP, S>(a, col, b, n, gid, NG, sub, gsp);
+    bwd_edges<LP, S>(a, col, b, n, p.gid, p.NG, p.sub, gsp);
     __syncthreads();  // red is free (the tile's previous hub was read)
 #pragma unroll
     for (int i = 0; i < S; ++i) {
 #pragma unroll
-      for (int m = LP; m < kMaxWave; m <<= 1) gsp[i] = gsp[i] + __shfl_xor(gsp[i], m, kMaxWave);
-      if (g == 0 && sub + LP * i < k) red[wave][sub + LP * i] = gsp[i];
+      for (int m = LP; m < kWave; m <<= 1) gsp[i] = gsp[i] + __shfl_xor(gsp[i], m, kWave);
+      if (p.g == 0 && p.sub + LP * i < k) red[p.wave][p.sub + LP * i] = gsp[i];
     }
     __syncthreads();
-    for (int l = tid; l < k; l += kMaxThreads)
+    for (int l = p.tid; l < k; l += lg::kThreads)
       a.grad_sp[col * k + l] = (red[0][l] + red[1][l]) + (red[2][l] + red[3][l]);
   }
 }
 
 // ------------------------------------------------------------------------------ entry points
-// sizes, k and strides shared by both calls; strides are resolved (0: the row width)
-static int check_shape(const std::string& w, int32_t num_rows, int32_t num_cols, int64_t E,
-                       int32_t D, int32_t k, int64_t& is) {
-  MAXK_CHECK_ARG(num_rows >= 0 && num_cols >= 0 && E >= 0 && E <= (int64_t)INT32_MAX,
-                 w + "sizes out of range");
-  MAXK_CHECK_ARG(D >= 1 && D <= maxk::kMaxDim, w + "dim_origin must be in [1, 256]");
-  MAXK_CHECK_ARG(k >= 1 && k <= D, w + "k must be between 1 and input dimension");
-  if (is == 0) is = k;
-  MAXK_CHECK_ARG(is >= k, w + "index_stride must be >= k (0: k)");
-  MAXK_CHECK_ARG(E == 0 || num_cols > 0, w + "sizes out of range: edges without columns");
-  MAXK_CHECK_ARG(E == 0 || num_rows > 0, w + "sizes out of range: edges without rows");
-  return MAXK_OK;
-}
-
 static int forward_impl(const int32_t* ptr, const int32_t* idx, const float* sp_data, int64_t ds,
                         const uint8_t* sp_index, int64_t is, float* out, int32_t* arg_edge,
                         uint8_t* arg_slot, int32_t N, int32_t NC, int64_t E, int32_t D, int32_t k,
                         void* stream) {
   const std::string w("maxk_max_aggregate_forward: ");
-  int rc = check_shape(w, N, NC, E, D, k, is);
+  int rc = lg::check_shape(w, N, NC, E, D, k, is);
   if (rc != MAXK_OK) return rc;
   if (ds == 0) ds = k;
   MAXK_CHECK_ARG(ds >= k, w + "data_stride must be >= k (0: k)");
@@ -426,14 +376,13 @@ static int forward_impl(const int32_t* ptr, const int32_t* idx, const float* sp_
   rc = check_ranges(w, ins, 4, outs, 3);
   if (rc != MAXK_OK) return rc;
   const FwdArgs a{ptr, idx, sp_data, ds, sp_index, is, out, arg_edge, arg_slot, N, NC, E, D, k};
-  const dim3 grid((unsigned)(((int64_t)N + kMaxTile - 1) / kMaxTile));
   if (int e = maxk::dispatch_variant(
           kMaxFwdVariants, select_max_fwd_variant(k, arg), [&](auto i) -> int {
             constexpr MaxFwdVariant v = kMaxFwdVariants[decltype(i)::value];
             const size_t lds = (size_t)max_fwd_states(v.lp) * (size_t)D * 12 +
-                               (size_t)(kMaxThreads / v.lp) * kFwdEdgesInFlight * kSeenWords * 4;
-            hipLaunchKernelGGL((max_fwd_kernel<v.lp, v.arg>), grid, dim3(kMaxThreads), lds,
-                               (hipStream_t)stream, a);
+                               (size_t)(lg::kThreads / v.lp) * kFwdEdgesInFlight * kSeenWords * 4;
+            hipLaunchKernelGGL((max_fwd_kernel<v.lp, v.arg>), lg::tile_grid(N),
+                               dim3(lg::kThreads), lds, (hipStream_t)stream, a);
             return MAXK_OK;
           }))
     return e;
@@ -447,7 +396,7 @@ static int backward_impl(const int32_t* ptr_t, const int32_t* idx_t, const int32
                          float* grad_sp, int32_t N, int32_t NC, int64_t E, int32_t D, int32_t k,
                          void* stream) {
   const std::string w("maxk_max_aggregate_backward: ");
-  int rc = check_shape(w, N, NC, E, D, k, is);
+  int rc = lg::check_shape(w, N, NC, E, D, k, is);
   if (rc != MAXK_OK) return rc;
   if (gs == 0) gs = D;
   MAXK_CHECK_ARG(gs >= D, w + "grad_stride must be >= dim_origin (0: dim_origin)");
@@ -469,11 +418,10 @@ static int backward_impl(const int32_t* ptr_t, const int32_t* idx_t, const int32
   if (rc != MAXK_OK) return rc;
   const BwdArgs a{ptr_t, idx_t, order, grad_out, gs, arg_edge, arg_slot, sp_index, is, grad_sp,
                   N, NC, E, D, k};
-  const dim3 grid((unsigned)(((int64_t)NC + kMaxTile - 1) / kMaxTile));
   if (int e = maxk::dispatch_variant(
           kMaxBwdVariants, select_max_bwd_variant(k), [&](auto i) -> int {
             constexpr int LP = kMaxBwdVariants[decltype(i)::value].lp;
-            hipLaunchKernelGGL(max_bwd_kernel<LP>, grid, dim3(kMaxThreads), 0,
+            hipLaunchKernelGGL(max_bwd_kernel<LP>, lg::tile_grid(NC), dim3(lg::kThreads), 0,
                                (hipStream_t)stream, a);
             return MAXK_OK;
           }))
@@ -508,6 +456,7 @@ extern "C" int maxk_max_aggregate_backward(const int32_t* ptr_t, const int32_t* 
 }
 
 extern "C" int maxk_max_row_limits(int32_t* out, int32_t capacity) {
-  return maxk::copy_limits(out, capacity, {maxk_mx::kMaxShortMax, maxk_mx::kMaxMediumMax,
-                                            maxk_mx::kMaxShortMax, maxk_mx::kMaxMediumMax});
+  namespace lg = maxk::lg;
+  return maxk::copy_limits(out, capacity,
+                           {lg::kShortMax, lg::kMediumMax, lg::kShortMax, lg::kMediumMax});
 }

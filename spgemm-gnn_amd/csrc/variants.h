@@ -25,11 +25,16 @@ constexpr int kTopkRows8 = 1 << 20;
 namespace variants_detail {
 inline std::string arg(int v) { return std::to_string(v); }
 inline std::string arg(bool v) { return v ? "true" : "false"; }
+// ns::kernel<a, ...> as the compiler's demangled name spells it
 template <class... A>
-std::string name(const char* kernel, A... a) {
-  std::string s = std::string("maxk::") + kernel + "<", sep;
+std::string name_in(const char* ns, const char* kernel, A... a) {
+  std::string s = std::string(ns) + "::" + kernel + "<", sep;
   ((s += sep + arg(a), sep = ", "), ...);
   return s + ">";
+}
+template <class... A>
+std::string name(const char* kernel, A... a) {
+  return name_in("maxk", kernel, a...);
 }
 }  // namespace variants_detail
 

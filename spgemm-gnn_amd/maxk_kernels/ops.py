@@ -79,6 +79,12 @@ def _check_tensor(t: torch.Tensor, name: str, dtype: Optional[torch.dtype] = Non
         _need(t.dtype == dtype, f"{name} must be {str(dtype).replace('torch.', '')}")
 
 
+def _check_ptr(ptr, name: str, count: str) -> None:
+    """A row-pointer array: int32, one entry more than the ``count`` it is named after."""
+    _check_tensor(ptr, name, torch.int32)
+    _need(ptr.dim() == 1 and ptr.numel() >= 1, f"{name} must have {count}+1 entries")
+
+
 def _table(t: torch.Tensor, name: str, dtype: torch.dtype, rows: int, k: int) -> int:
     """A [rows, k] CBSR table whose rows may be strided (interleaved records): returns the row
     stride in elements."""
@@ -751,8 +757,7 @@ def _edge_softmax_args(ptr, tensors, names, out):
     """The checks shared by :func:`edge_softmax` and :func:`edge_softmax_backward`: ``ptr`` int32
     ``[num_rows + 1]``, every tensor of ``tensors`` contiguous f32 ``[num_edges]`` on ``ptr``'s
     device. Returns ``(num_rows, num_edges, out)``."""
-    _check_tensor(ptr, "ptr", torch.int32)
-    _need(ptr.dim() == 1 and ptr.numel() >= 1, "ptr must have num_rows+1 entries")
+    _check_ptr(ptr, "ptr", "num_rows")
     dev = ptr.device
     num_edges = None
     for t, name in zip(tensors, names):
@@ -821,8 +826,7 @@ def _gat_attention_args(ptr, idx, el, er):
     """The checks shared by :func:`gat_attention` and :func:`gat_attention_backward`: ``ptr``
     int32 ``[num_rows + 1]``, ``idx`` int32 ``[num_edges]``, ``el`` f32 ``[num_cols]``, ``er`` f32
     ``[num_rows]`` on ``ptr``'s device. Returns ``(num_rows, num_cols, num_edges)``."""
-    _check_tensor(ptr, "ptr", torch.int32)
-    _need(ptr.dim() == 1 and ptr.numel() >= 1, "ptr must have num_rows+1 entries")
+    _check_ptr(ptr, "ptr", "num_rows")
     dev = ptr.device
     _vector(idx, "idx", torch.int32, None, "num_edges", dev)
     _vector(el, "el", torch.float32, None, "num_cols", dev)
@@ -885,8 +889,7 @@ def edge_colsum(ptr_t, order, values, out: Optional[torch.Tensor] = None) -> tor
     ``out[c] = sum_j values[order[j]]`` for ``j`` in ``[ptr_t[c], ptr_t[c + 1])``, with ``ptr_t``
     int32 ``[num_cols + 1]`` and ``order`` int32 ``[num_edges]`` the transposed structure of the
     graph (``CSRGraph.transposed_structure()[0]`` and ``CSRGraph.transposed_order()``)."""
-    _check_tensor(ptr_t, "ptr_t", torch.int32)
-    _need(ptr_t.dim() == 1 and ptr_t.numel() >= 1, "ptr_t must have num_cols+1 entries")
+    _check_ptr(ptr_t, "ptr_t", "num_cols")
     dev = ptr_t.device
     _vector(order, "order", torch.int32, None, "num_edges", dev)
     _vector(values, "values", torch.float32, order.numel(), "num_edges", dev)
@@ -920,8 +923,7 @@ def _out_matrix(out, name: str, rows: int, cols: int, shape_name: str, dev) -> t
 def _gat_heads_args(ptr, idx, el, er):
     """``ptr`` int32 ``[num_rows + 1]``, ``idx`` int32 ``[num_edges]``, ``el`` f32 ``[H,
     num_cols]``, ``er`` f32 ``[H, num_rows]``. Returns ``(H, num_rows, num_cols, num_edges)``."""
-    _check_tensor(ptr, "ptr", torch.int32)
-    _need(ptr.dim() == 1 and ptr.numel() >= 1, "ptr must have num_rows+1 entries")
+    _check_ptr(ptr, "ptr", "num_rows")
     dev = ptr.device
     _vector(idx, "idx", torch.int32, None, "num_edges", dev)
     _matrix(el, "el", None, None, "num_heads, num_cols", dev)
@@ -968,8 +970,7 @@ def gat_attention_backward_heads(ptr, idx, el, er, negative_slope: float, alpha,
 def edge_colsum_heads(ptr_t, order, values, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """:func:`edge_colsum` of ``values`` f32 ``[H, num_edges]`` per head: f32 ``[H, num_cols]``
     (``maxk_edge_colsum_heads``)."""
-    _check_tensor(ptr_t, "ptr_t", torch.int32)
-    _need(ptr_t.dim() == 1 and ptr_t.numel() >= 1, "ptr_t must have num_cols+1 entries")
+    _check_ptr(ptr_t, "ptr_t", "num_cols")
     dev = ptr_t.device
     _vector(order, "order", torch.int32, None, "num_edges", dev)
     _matrix(values, "values", None, order.numel(), "num_heads, num_edges", dev)
@@ -994,6 +995,28 @@ def _heads_tables(sp_data, sp_index, dev):
     return num_cols, k, ds, is_
 
 
+_NO_ALPHA = object()
+
+
+def _aggregate_backward_args(ptr_t, idx_t, order, grad_out, alpha=_NO_ALPHA):
+    """The transposed structure and the ``grad_out`` table of an aggregation's backward, with the
+    head-major ``alpha [H, num_edges]`` of the multi-head one checked between them:
+    ``(device, num_edges, num_rows, dim_origin, grad_stride)``."""
+    _check_ptr(ptr_t, "ptr_t", "num_cols")
+    dev = ptr_t.device
+    _vector(order, "order", torch.int32, None, "num_edges", dev)
+    e = order.numel()
+    _vector(idx_t, "idx_t", torch.int32, e, "num_edges", dev)
+    if alpha is not _NO_ALPHA:
+        _matrix(alpha, "alpha", None, e, "num_heads, num_edges", dev)
+    _need(isinstance(grad_out, torch.Tensor) and grad_out.dim() == 2,
+          "grad_out must be [num_rows, dim_origin]")
+    n, d = grad_out.shape
+    gs = _table(grad_out, "grad_out", torch.float32, n, d)
+    _need(grad_out.device == dev, "all tensors must be on the same device")
+    return dev, e, n, d, gs
+
+
 def heads_aggregate(ptr, idx, alpha, sp_data, sp_index, dim_origin: int,
                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Multi-head weighted aggregation of CBSR features, f32 ``[num_rows, dim_origin]``:
@@ -1001,8 +1024,7 @@ def heads_aggregate(ptr, idx, alpha, sp_data, sp_index, dim_origin: int,
     f32 ``[H, num_edges]`` head-major, ``F = dim_origin // H`` and ``X`` the densified tables
     (``maxk_heads_aggregate_forward``; contract in include/maxk_hip.h, "Multi-head
     aggregation"). No plan is built or used."""
-    _check_tensor(ptr, "ptr", torch.int32)
-    _need(ptr.dim() == 1 and ptr.numel() >= 1, "ptr must have num_rows+1 entries")
+    _check_ptr(ptr, "ptr", "num_rows")
     dev = ptr.device
     _vector(idx, "idx", torch.int32, None, "num_edges", dev)
     e, n = idx.numel(), ptr.numel() - 1
@@ -1027,19 +1049,8 @@ def heads_aggregate_backward(ptr_t, idx_t, order, alpha, grad_out, sp_data, sp_i
     may be strided) over the transposed structure ``(ptr_t, idx_t, order)``, all int32
     (``maxk_heads_aggregate_backward``). A half that is not needed is not computed; nothing is
     launched when neither is."""
-    _check_tensor(ptr_t, "ptr_t", torch.int32)
-    _need(ptr_t.dim() == 1 and ptr_t.numel() >= 1, "ptr_t must have num_cols+1 entries")
-    dev = ptr_t.device
-    _vector(order, "order", torch.int32, None, "num_edges", dev)
-    e = order.numel()
-    _vector(idx_t, "idx_t", torch.int32, e, "num_edges", dev)
-    _matrix(alpha, "alpha", None, e, "num_heads, num_edges", dev)
+    dev, e, n, d, gs = _aggregate_backward_args(ptr_t, idx_t, order, grad_out, alpha)
     h = alpha.shape[0]
-    _need(isinstance(grad_out, torch.Tensor) and grad_out.dim() == 2,
-          "grad_out must be [num_rows, dim_origin]")
-    n, d = grad_out.shape
-    gs = _table(grad_out, "grad_out", torch.float32, n, d)
-    _need(grad_out.device == dev, "all tensors must be on the same device")
     _need(1 <= h and d % max(h, 1) == 0,
           "the number of heads (alpha.shape[0]) must divide dim_origin")
     num_cols, k, ds, is_ = _heads_tables(sp_data, sp_index, dev)
@@ -1077,8 +1088,7 @@ def max_aggregate_forward(ptr, idx, sp_data, sp_index, dim_origin: int, with_arg
     the implicit zero). ``with_arg=False`` writes ``out`` alone, with the same bits
     (``maxk_max_aggregate_forward``). Rows of 2^24 edges or more are not supported and not
     checked here (:func:`maxk_kernels.max_aggregate` checks its graph once)."""
-    _check_tensor(ptr, "ptr", torch.int32)
-    _need(ptr.dim() == 1 and ptr.numel() >= 1, "ptr must have num_rows+1 entries")
+    _check_ptr(ptr, "ptr", "num_rows")
     dev = ptr.device
     _vector(idx, "idx", torch.int32, None, "num_edges", dev)
     e, n = idx.numel(), ptr.numel() - 1
@@ -1101,17 +1111,7 @@ def max_aggregate_backward(ptr_t, idx_t, order, grad_out, arg_edge, arg_slot,
     (f32 ``[num_rows, dim_origin]``, rows may be strided) goes to the slot that ``arg_edge`` /
     ``arg_slot`` name, summed per slot over the transposed structure ``(ptr_t, idx_t, order)``,
     all int32 (``maxk_max_aggregate_backward``)."""
-    _check_tensor(ptr_t, "ptr_t", torch.int32)
-    _need(ptr_t.dim() == 1 and ptr_t.numel() >= 1, "ptr_t must have num_cols+1 entries")
-    dev = ptr_t.device
-    _vector(order, "order", torch.int32, None, "num_edges", dev)
-    e = order.numel()
-    _vector(idx_t, "idx_t", torch.int32, e, "num_edges", dev)
-    _need(isinstance(grad_out, torch.Tensor) and grad_out.dim() == 2,
-          "grad_out must be [num_rows, dim_origin]")
-    n, d = grad_out.shape
-    gs = _table(grad_out, "grad_out", torch.float32, n, d)
-    _need(grad_out.device == dev, "all tensors must be on the same device")
+    dev, e, n, d, gs = _aggregate_backward_args(ptr_t, idx_t, order, grad_out)
     for t, name, dtype in ((arg_edge, "arg_edge", torch.int32), (arg_slot, "arg_slot", torch.uint8)):
         _check_tensor(t, name, dtype)
         _need(tuple(t.shape) == (n, d) and t.device == dev,
@@ -1164,8 +1164,7 @@ def sample_neighbors(ptr, idx, seeds, fanout: int, seed: int, out=None, scratch=
     pre-allocated (``capacity = out[1].numel()``; default :func:`sample_capacity`); ``scratch``: a
     u8 buffer of :func:`sample_scratch_bytes` bytes. With both given the call allocates nothing
     and can be captured into a graph."""
-    _check_tensor(ptr, "ptr", torch.int32)
-    _need(ptr.dim() == 1 and ptr.numel() >= 1, "ptr must have num_rows+1 entries")
+    _check_ptr(ptr, "ptr", "num_rows")
     dev = ptr.device
     _vector(idx, "idx", torch.int32, None, "num_edges", dev)
     _vector(seeds, "seeds", torch.int32, None, "num_seeds", dev)
@@ -1242,8 +1241,7 @@ def induced_subgraph_scratch_bytes(num_nodes: int, num_sel: int) -> int:
 
 
 def _subgraph_args(ptr, idx, nodes):
-    _check_tensor(ptr, "ptr", torch.int32)
-    _need(ptr.dim() == 1 and ptr.numel() >= 1, "ptr must have num_nodes+1 entries")
+    _check_ptr(ptr, "ptr", "num_nodes")
     dev = ptr.device
     _vector(idx, "idx", torch.int32, None, "num_edges", dev)
     _vector(nodes, "nodes", torch.int32, None, "num_sel", dev)
@@ -1325,8 +1323,7 @@ def csr_transpose(ptr, idx, val=None, num_cols: Optional[int] = None, out=None, 
     (returned when ``val`` is given). ``out``: the three or four buffers, pre-allocated;
     ``scratch``: a u8 buffer of :func:`csr_transpose_scratch_bytes` bytes. With both given the
     call allocates nothing and can be captured into a graph."""
-    _check_tensor(ptr, "ptr", torch.int32)
-    _need(ptr.dim() == 1 and ptr.numel() >= 1, "ptr must have num_rows+1 entries")
+    _check_ptr(ptr, "ptr", "num_rows")
     dev = ptr.device
     _vector(idx, "idx", torch.int32, None, "num_edges", dev)
     n, e = ptr.numel() - 1, idx.numel()

@@ -108,6 +108,58 @@ def transposed(ptr, idx, num_cols):
     return ptr_t.astype(np.int32), rows[order].astype(np.int32), order.astype(np.int32)
 
 
+# One tile of 16 rows holds two adjacent hubs, a medium, a short and an empty row; the next is all
+# short; row 32 is alone in the last tile (15 positions past num_rows), medium at exactly the limit.
+TILE_ROWS, TILE_COLS = 33, 700
+TILE_LENGTHS = {0: 600, 1: LIMITS[1] + 1, 2: LIMITS[0] + 1, 3: LIMITS[0], 4: 0, 32: LIMITS[1]}
+
+
+@functools.lru_cache(maxsize=None)
+def tile_graph():
+    """(ptr, idx) int32 of the 33 x 700 graph above; rows 5 .. 31 are short, of random length."""
+    rng = np.random.default_rng(33)
+    lengths = rng.integers(0, LIMITS[0] + 1, TILE_ROWS)
+    for r, n in TILE_LENGTHS.items():
+        lengths[r] = n
+    rows = np.repeat(np.arange(TILE_ROWS), lengths)
+    ptr, idx = csr_from_edges(rows, rng.integers(0, TILE_COLS, rows.size), TILE_ROWS)
+    want = [2, 2, 1, 0, 0] + [0] * 27 + [1]
+    assert [regime(int(n)) for n in np.diff(ptr)] == want
+    for a in (ptr, idx):
+        a.setflags(write=False)
+    return ptr, idx
+
+
+@functools.lru_cache(maxsize=None)
+def tile_graph_t():
+    """(ptr, idx) of the 700 x 33 graph whose columns have tile_graph's row lengths, for the
+    backward's walk over columns; its rows are short."""
+    ptr, idx = tile_graph()
+    tp, ti = csr_from_edges(idx.astype(np.int64), rows_of(ptr), TILE_COLS)
+    assert np.array_equal(np.bincount(ti, minlength=TILE_ROWS), np.diff(ptr))
+    for a in (tp, ti):
+        a.setflags(write=False)
+    return tp, ti
+
+
+@functools.lru_cache(maxsize=None)
+def short_graph(n):
+    """(ptr, idx) of an n x n graph whose rows and columns are all short: row 0 and every fourth
+    row after it at exactly the short limit (or n, if that is less), some rows empty."""
+    rng = np.random.default_rng(100 + n)
+    top = min(n, LIMITS[0])
+    lengths = rng.integers(0, min(n, 6) + 1, n)
+    lengths[::4] = top
+    rows = np.repeat(np.arange(n), lengths)
+    ptr, idx = csr_from_edges(rows, rng.integers(0, n, rows.size), n)
+    rlen, clen = np.diff(ptr), np.bincount(idx, minlength=n)
+    assert max(rlen.max(), clen.max()) <= LIMITS[0] and (rlen == top).sum() >= (n + 3) // 4
+    assert n == 1 or (rlen == 0).any()
+    for a in (ptr, idx):
+        a.setflags(write=False)
+    return ptr, idx
+
+
 def small_graph(n=40, seed=2):
     rng = np.random.default_rng(seed)
     deg = rng.integers(0, 9, n)

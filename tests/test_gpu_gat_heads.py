@@ -857,7 +857,87 @@ def test_layer_refusals_and_one_head_unchanged(gpu):
     same_bits(out.detach().cpu().numpy(), want.detach().cpu().numpy(), "num_heads=1")
 
 
-# ------------------------------------------------------------------ 11. closure (keep last)
+# ------------------------------------------------------------------ 11. the tile walk
+# What the three passes over a tile can get wrong and the 600 x 600 graph does not reach: two hubs
+# in one tile (row state 0 and `red` used twice), a tile of short rows alone, a last tile with
+# one row, and row counts around one tile. Exact inputs, bit for bit.
+def walk_graph(which):
+    """(ptr, idx, num_cols) of gh.tile_graph ("tile"), gh.tile_graph_t ("tile_t") or
+    gh.short_graph(which)."""
+    if which == "tile":
+        return gh.tile_graph() + (gh.TILE_COLS,)
+    if which == "tile_t":
+        return gh.tile_graph_t() + (gh.TILE_ROWS,)
+    return gh.short_graph(which) + (which,)
+
+
+@functools.lru_cache(maxsize=None)
+def walk_case(which, D, H, k):
+    ptr, idx, nc = walk_graph(which)
+    data, sel = gh.tables(nc, D, k, seed=D + H + k, exact=True)
+    alpha = gh.exact_alpha(H, idx.size, seed=k)
+    g = gh.exact_grad(ptr.size - 1, D, seed=H)
+    out, mag, _ = gh.forward64(ptr, idx, alpha, data, sel, D)
+    (gsp, smag, _), (ga, amag, _) = gh.backward64(ptr, idx, alpha, g, data, sel, D)
+    assert max(mag.max(), smag.max(), amag.max()) * 8 < 2 ** 23      # exactly summable
+    return data, sel, alpha, g, out.astype(np.float32), gsp.astype(np.float32), \
+        ga.astype(np.float32)
+
+
+def walk_dev(which, dev):
+    ptr, idx, nc = walk_graph(which)
+    return tuple(dev_of(a, dev) for a in (ptr, idx) + gh.transposed(ptr, idx, nc))
+
+
+# LP = 8 and LP = 64 with two slots per lane, one head and sixteen (F = 4 at D = 64)
+WALK_SHAPES = [(64, 1, 8), (64, 16, 8), (256, 1, 96), (256, 16, 96)]
+
+
+@pytest.mark.parametrize("D,H,k", WALK_SHAPES)
+def test_two_hub_rows_share_a_tile(gpu, D, H, k):
+    names = launch_names(D, H, k)
+    data, sel, alpha, _, out, _, _ = walk_case("tile", D, H, k)
+    data, sel, alpha = (dev_of(a, gpu) for a in (data, sel, alpha))
+    got = fwd(gpu, alpha, data, sel, D, graph=walk_dev("tile", gpu))
+    same_bits(got.cpu().numpy(), out, "out")
+    COVERED.add(names[0])
+
+
+@pytest.mark.parametrize("D,H,k", WALK_SHAPES)
+def test_two_hub_columns_share_a_tile(gpu, D, H, k):
+    names = launch_names(D, H, k)
+    data, sel, alpha, g, _, gsp, ga = walk_case("tile_t", D, H, k)
+    data, sel, alpha, g = (dev_of(a, gpu) for a in (data, sel, alpha, g))
+    graph = walk_dev("tile_t", gpu)
+    for need_sp, need_alpha in ((True, False), (False, True), (True, True)):
+        got_sp, got_a = bwd(gpu, alpha, g, data, sel, need_sp, need_alpha, graph=graph)
+        assert (got_sp is None) == (not need_sp) and (got_a is None) == (not need_alpha)
+        if need_sp:
+            same_bits(got_sp.cpu().numpy(), gsp, f"grad_sp ({need_sp}, {need_alpha})")
+        if need_alpha:
+            same_bits(got_a.cpu().numpy(), ga, f"grad_alpha ({need_sp}, {need_alpha})")
+    COVERED.add(names[1])
+
+
+@pytest.mark.parametrize("H", [1, 8])
+@pytest.mark.parametrize("n", [1, 15, 16, 17])
+def test_row_counts_around_one_tile(gpu, n, H, D=256, k=16):
+    names = launch_names(D, H, k)
+    data, sel, alpha, g, out, gsp, ga = walk_case(n, D, H, k)
+    data, sel, alpha, g = (dev_of(a, gpu) for a in (data, sel, alpha, g))
+    graph = walk_dev(n, gpu)
+    same_bits(fwd(gpu, alpha, data, sel, D, graph=graph).cpu().numpy(), out, "out")
+    for need_sp, need_alpha in ((True, False), (False, True), (True, True)):
+        got_sp, got_a = bwd(gpu, alpha, g, data, sel, need_sp, need_alpha, graph=graph)
+        assert (got_sp is None) == (not need_sp) and (got_a is None) == (not need_alpha)
+        if need_sp:
+            same_bits(got_sp.cpu().numpy(), gsp, f"grad_sp ({need_sp}, {need_alpha})")
+        if need_alpha:
+            same_bits(got_a.cpu().numpy(), ga, f"grad_alpha ({need_sp}, {need_alpha})")
+    COVERED.update(names)
+
+
+# ------------------------------------------------------------------ 12. closure (keep last)
 def test_every_heads_instantiation_was_launched_by_a_passing_case(gpu):
     with open(FIXTURE) as f:
         names = {ln.strip() for ln in f if ln.strip()}

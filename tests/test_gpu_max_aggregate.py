@@ -668,7 +668,80 @@ def test_sage_model_with_the_pool_aggregator_trains_one_step(gpu):
         assert bool(torch.isfinite(model(graph, x)).all())
 
 
-# ------------------------------------------------------------------ 10. closure (keep last)
+# ------------------------------------------------------------------ 10. the tile walk
+# What the three passes over a tile can get wrong and the 600 x 600 graph does not reach: two hubs
+# in one tile (row state 0 and `red` used twice), a tile of short rows alone, a last tile with
+# one row, and row counts around one tile. Tie-heavy exact tables, bit for bit.
+def walk_graph(which):
+    """(ptr, idx, num_cols) of gh.tile_graph ("tile"), gh.tile_graph_t ("tile_t") or
+    gh.short_graph(which)."""
+    if which == "tile":
+        return mx.gh.tile_graph() + (mx.gh.TILE_COLS,)
+    if which == "tile_t":
+        return mx.gh.tile_graph_t() + (mx.gh.TILE_ROWS,)
+    return mx.gh.short_graph(which) + (which,)
+
+
+@functools.lru_cache(maxsize=None)
+def walk_case(which, D, k):
+    """(data, sel, out, arg_edge, arg_slot, grad_out, grad_sp) of exact tables on the graph."""
+    ptr, idx, nc = walk_graph(which)
+    data, sel = mx.tables(nc, D, k, seed=D + k, exact=True)
+    out, ae, sl = mx.forward_ref(ptr, idx, data, sel, D)
+    g = mx.exact_grad(ptr.size - 1, D, seed=D + k)
+    gsp, mag, _ = mx.backward64(ptr, idx, g, ae, sl, sel)
+    assert mag.max() * 2 < 2 ** 24          # exactly summable: quanta of 1/2
+    return data, sel, out, ae, sl, g, gsp.astype(np.float32)
+
+
+def walk_dev(which, dev):
+    ptr, idx, nc = walk_graph(which)
+    return tuple(dev_of(a, dev) for a in (ptr, idx) + mx.transposed(ptr, idx, nc))
+
+
+def walk_forward(dev, which, D, k):
+    data, sel, out, ae, sl, _, _ = walk_case(which, D, k)
+    data, sel = dev_of(data, dev), dev_of(sel, dev)
+    graph = walk_dev(which, dev)
+    same_forward(fwd(dev, data, sel, D, graph=graph), (out, ae, sl), f"{which}")
+    alone = fwd(dev, data, sel, D, with_arg=False, graph=graph)[0]
+    same_bits(alone.cpu().numpy(), out, f"{which}: out without arg_*")
+
+
+def walk_backward(dev, which, D, k):
+    _, sel, _, ae, sl, g, gsp = walk_case(which, D, k)
+    sel, ae, sl, g = (dev_of(a, dev) for a in (sel, ae, sl, g))
+    got = bwd(dev, g, ae, sl, sel, graph=walk_dev(which, dev))
+    same_bits(got.cpu().numpy(), gsp, f"{which}: grad_sp")
+
+
+# LP = 8, and LP = 64 with two slots per lane
+WALK_SHAPES = [(64, 8), (256, 96)]
+
+
+@pytest.mark.parametrize("D,k", WALK_SHAPES)
+def test_two_hub_rows_share_a_tile(gpu, D, k):
+    names = launch_names(k)[:2]
+    walk_forward(gpu, "tile", D, k)
+    COVERED.update(names)
+
+
+@pytest.mark.parametrize("D,k", WALK_SHAPES)
+def test_two_hub_columns_share_a_tile(gpu, D, k):
+    names = launch_names(k)[2:]
+    walk_backward(gpu, "tile_t", D, k)
+    COVERED.update(names)
+
+
+@pytest.mark.parametrize("n", [1, 15, 16, 17])
+def test_row_counts_around_one_tile(gpu, n, D=256, k=16):
+    names = launch_names(k)
+    walk_forward(gpu, n, D, k)
+    walk_backward(gpu, n, D, k)
+    COVERED.update(names)
+
+
+# ------------------------------------------------------------------ 11. closure (keep last)
 def test_every_max_instantiation_was_launched_by_a_passing_case(gpu):
     with open(FIXTURE) as f:
         names = {ln.strip() for ln in f if ln.strip()}
