@@ -11,6 +11,13 @@ module that does not exist) and its ``MaxKFunction`` (utils/maxk_layers.py:16-45
 * :class:`SpGEMMFunction` maps CBSR features to ``Y = A @ densify(sp)`` (SpGEMM forward)
   and back-propagates with the SSpMM kernel, ``grad_sp = (A^T G)`` sampled at the
   selector.
+* :class:`MaxKAggregateFunction` and :class:`MaxKSelfAggregateFunction` fuse the two, and
+  :class:`EdgeWeightedFunction` does so with changing edge values. All three run one forward,
+  :func:`_fused_forward` (the top-k writing what the plan's forward gathers, then that
+  forward), and one input gradient, :func:`_maxk_input_grad` (padding, the merge of the dense
+  row's gradient, the scatter), which is also the whole backward of :class:`MaxKFunction`. A
+  Function picks the plan, records on ``ctx``, and in the backward checks or refreshes the edge
+  values before the SSpMM.
 * :class:`EdgeWeightedFunction` is the aggregation with the edge values as a differentiable
   input (``edge_weight=`` on :func:`spgemm`, :func:`maxk_aggregate`,
   :func:`maxk_self_aggregate`): the same kernels on a value-refreshed plan, plus the SDDMM
@@ -311,6 +318,53 @@ def _mask_padding(grad_data, sp_index, count):
     return grad_data, sp_index
 
 
+def _fused_forward(plan, x, k, mode, dropout, dense, keep_values):
+    """One top-k launch feeding ``plan``'s forward: ``(out, sp_index, count, sp_data)``. Where
+    the plan's forward gathers records the top-k writes them (GraphPlan.new_records) next to a
+    plain selector table, and the plain ``[N, k]`` value table only with ``keep_values``; else it
+    writes the plan's two tables (GraphPlan.new_cbsr). The statistics pair comes with the top-k
+    only for a fixed-point forward, the only one that reads it. ``dense``: the ``[N, D]`` tensor
+    that receives the dense masked row, or None. ``count`` is None in exact mode, ``sp_data``
+    None without ``keep_values``."""
+    stats = torch.empty(2, dtype=torch.int32, device=x.device) if plan.fwd_fixed else None
+    st2 = stats.view(1, 2) if stats is not None else None
+    rec = plan.new_records()
+    if rec is not None:
+        res = ops.maxk_forward(x, k, mode=mode, return_index=True, records=rec,
+                               return_values=keep_values, stats=stats,
+                               return_count=mode != "exact", dropout=dropout, dense=dense)
+        out = plan.forward_records(rec[0], rec[1], stats=st2)
+    else:
+        res = ops.maxk_forward(x, k, mode=mode, return_index=True, out=plan.new_cbsr(),
+                               stats=stats, return_count=mode != "exact", dropout=dropout,
+                               dense=dense)
+        out = plan.forward(res[0], res[1], stats=st2)
+    return out, res[1], res[2] if len(res) == 3 else None, res[0] if keep_values else None
+
+
+def _maxk_input_grad(grad_sp, sp_index, count, dim_origin, dropout, g_self):
+    """The gradient of the MaxK input from ``grad_sp [N, k]``, the gradient of the kept values
+    (None: nothing came through them), and ``g_self [N, D]``, the gradient of the dense masked
+    row (or None), merged by one scatter. ``count`` (ref_compat): the filled slots per row. A
+    padding slot is pointed at the row's last filled slot with that slot's gradient
+    (:func:`_mask_padding`), so the last slot still wins with the same sum; the dropout mask is
+    keyed on the feature, so the padding slot gets that slot's mask too."""
+    if count is not None:
+        if grad_sp is None:
+            grad_sp = torch.zeros(sp_index.shape, dtype=torch.float32, device=sp_index.device)
+        grad_sp, sp_index = _mask_padding(grad_sp, sp_index, count)
+    if g_self is not None:
+        g_self = ops._rows_in_place(g_self)
+    grad_x = ops.maxk_backward(grad_sp, sp_index, dim_origin=dim_origin, dropout=dropout,
+                               grad_dense=g_self)
+    if count is not None and g_self is not None:
+        # a row that fills no slot (a constant row) has no last filled slot to point at: its
+        # slots stay (selector 0, gradient 0), which is harmless without g_self, but the merge
+        # would add g_self[r, 0] into a feature 0 that was not selected
+        grad_x.masked_fill_((count == 0)[:, None], 0.0)
+    return grad_x
+
+
 class MaxKFunction(torch.autograd.Function):
     """x [N, D] -> CBSR (sp_data, sp_index); backward = the device scatter of grad_data
     into the selected features (the ``grad * mask`` of utils/models.py:23-26).
@@ -340,14 +394,9 @@ class MaxKFunction(torch.autograd.Function):
     @first_order_only
     def backward(ctx, grad_data, grad_index):
         saved = ctx.saved_tensors
-        sp_index = saved[0]
-        grad_data = grad_data.contiguous()
-        if len(saved) == 2:
-            grad_data, sp_index = _mask_padding(grad_data, sp_index, saved[1])
-        # the mask is keyed on the feature, so a padding slot pointed at the last filled slot
-        # gets that slot's mask
-        grad_x = ops.maxk_backward(grad_data, sp_index, dim_origin=ctx.dim_origin,
-                                   dropout=ctx.dropout)
+        grad_x = _maxk_input_grad(grad_data.contiguous(), saved[0],
+                                  saved[1] if len(saved) == 2 else None, ctx.dim_origin,
+                                  ctx.dropout, None)
         return grad_x, None, None, None
 
 
@@ -407,15 +456,13 @@ class DenseAggFunction(torch.autograd.Function):
 
 class MaxKAggregateFunction(torch.autograd.Function):
     """``A @ densify(MaxK(x))`` as one producer-consumer pair (utils/maxk_layers.py:16-34:
-    MaxK feeding the SpGEMM). Where the plan's forward gathers records (``fwd_layout`` 1, 2 or
-    4: every default plan that packs), the top-k writes those records itself
-    (``maxk_topk_cbsr_records``, GraphPlan.new_records) next to a plain ``[N, k]`` selector
-    table for the backward, and the forward gathers them as they are
-    (GraphPlan.forward_records): it launches no per-call pack or statistics pass. Plans that
-    gather the two plain tables (``fwd_layout`` 0 and 3) get plain tables. The fixed-point
-    statistics of the emitted rows come with the top-k only when the forward runs fixed point
-    (``fwd_fixed``), which is the only forward that reads them. Backward: the SSpMM on the same
-    plan, then the MaxK scatter (same rules as MaxKFunction for ref_compat padding).
+    MaxK feeding the SpGEMM), :func:`_fused_forward`. Where the plan's forward gathers records
+    (``fwd_layout`` 1, 2 or 4: every default plan that packs), the top-k writes those records
+    itself (``maxk_topk_cbsr_records``) next to a plain ``[N, k]`` selector table for the
+    backward, and the forward gathers them as they are: it launches no per-call pack or
+    statistics pass, and no ``[N, k]`` value table is written. Plans that gather the two plain
+    tables (``fwd_layout`` 0 and 3) get plain tables. Backward: the SSpMM on the same plan, then
+    :func:`_maxk_input_grad` (same rules as MaxKFunction for ref_compat padding).
     ``dropout=(p, seed)``: feature dropout between the MaxK and the aggregation, inside the
     top-k (records and statistics are those of the dropped values, so still no pack and no
     statistics pass) and inside the scatter; the pair is kept on ``ctx``, no mask tensor."""
@@ -424,26 +471,12 @@ class MaxKAggregateFunction(torch.autograd.Function):
     def forward(ctx, x: torch.Tensor, graph: CSRGraph, k: int, mode: str = "exact",
                 dropout=None):
         x = x.contiguous()
-        d = x.shape[1]
-        plan = graph.plan(d, k)
-        stats = torch.empty(2, dtype=torch.int32, device=x.device) if plan.fwd_fixed else None
-        st2 = stats.view(1, 2) if stats is not None else None
-        rec = plan.new_records()
-        if rec is not None:
-            res = ops.maxk_forward(x, k, mode=mode, return_index=True, records=rec,
-                                   return_values=False, stats=stats,
-                                   return_count=mode != "exact", dropout=dropout)
-            sp_index = res[1]
-            out = plan.forward_records(rec[0], rec[1], stats=st2)
-        else:
-            sp_data, sp_index = plan.new_cbsr()
-            res = ops.maxk_forward(x, k, mode=mode, return_index=True, out=(sp_data, sp_index),
-                                   stats=stats, return_count=mode != "exact", dropout=dropout)
-            out = plan.forward(sp_data, sp_index, stats=st2)
-        ctx.save_for_backward(sp_index, *res[2:])
+        plan = graph.plan(x.shape[1], k)
+        out, sp_index, count, _ = _fused_forward(plan, x, k, mode, dropout, None, False)
+        ctx.save_for_backward(sp_index, *(() if count is None else (count,)))
         ctx.plan = plan
         ctx.dropout = dropout
-        ctx.dim_origin = d
+        ctx.dim_origin = x.shape[1]
         _save_values_version(ctx, graph.val)
         return out
 
@@ -451,15 +484,12 @@ class MaxKAggregateFunction(torch.autograd.Function):
     @first_order_only
     def backward(ctx, grad_out):
         saved = ctx.saved_tensors
-        sp_index = saved[0]
         grad_x = None
         if ctx.needs_input_grad[0]:
             _check_values_version(ctx)
-            grad_sp = ctx.plan.backward(grad_out.contiguous(), sp_index)
-            if len(saved) == 2:
-                grad_sp, sp_index = _mask_padding(grad_sp, sp_index, saved[1])
-            grad_x = ops.maxk_backward(grad_sp, sp_index, dim_origin=ctx.dim_origin,
-                                       dropout=ctx.dropout)
+            grad_sp = ctx.plan.backward(grad_out.contiguous(), saved[0])
+            grad_x = _maxk_input_grad(grad_sp, saved[0], saved[1] if len(saved) == 2 else None,
+                                      ctx.dim_origin, ctx.dropout, None)
         return grad_x, None, None, None, None
 
 
@@ -479,28 +509,13 @@ class MaxKSelfAggregateFunction(torch.autograd.Function):
     def forward(ctx, x: torch.Tensor, graph: CSRGraph, k: int, mode: str = "exact",
                 dropout=None):
         x = x.contiguous()
-        d = x.shape[1]
-        plan = graph.plan(d, k)
-        stats = torch.empty(2, dtype=torch.int32, device=x.device) if plan.fwd_fixed else None
-        st2 = stats.view(1, 2) if stats is not None else None
+        plan = graph.plan(x.shape[1], k)
         x_m = torch.empty_like(x)
-        rec = plan.new_records()
-        if rec is not None:
-            res = ops.maxk_forward(x, k, mode=mode, return_index=True, records=rec,
-                                   return_values=False, stats=stats,
-                                   return_count=mode != "exact", dropout=dropout, dense=x_m)
-            sp_index = res[1]
-            out = plan.forward_records(rec[0], rec[1], stats=st2)
-        else:
-            sp_data, sp_index = plan.new_cbsr()
-            res = ops.maxk_forward(x, k, mode=mode, return_index=True, out=(sp_data, sp_index),
-                                   stats=stats, return_count=mode != "exact", dropout=dropout,
-                                   dense=x_m)
-            out = plan.forward(sp_data, sp_index, stats=st2)
-        ctx.save_for_backward(sp_index, *res[2:])
+        out, sp_index, count, _ = _fused_forward(plan, x, k, mode, dropout, x_m, False)
+        ctx.save_for_backward(sp_index, *(() if count is None else (count,)))
         ctx.plan = plan
         ctx.dropout = dropout
-        ctx.dim_origin = d
+        ctx.dim_origin = x.shape[1]
         _save_values_version(ctx, graph.val)
         ctx.set_materialize_grads(False)  # an unused output arrives as None, not as zeros
         return x_m, out
@@ -509,29 +524,14 @@ class MaxKSelfAggregateFunction(torch.autograd.Function):
     @first_order_only
     def backward(ctx, g_self, g_agg):
         saved = ctx.saved_tensors
-        sp_index = saved[0]
         if not ctx.needs_input_grad[0] or (g_self is None and g_agg is None):
             return None, None, None, None, None
         grad_sp = None
         if g_agg is not None:
             _check_values_version(ctx)
-            grad_sp = ctx.plan.backward(g_agg.contiguous(), sp_index)
-        if len(saved) == 2:
-            # a padding slot repeats the last filled slot's selector and gradient, so the last
-            # slot still wins with the same sum
-            if grad_sp is None:
-                grad_sp = torch.zeros(sp_index.shape, dtype=torch.float32,
-                                      device=sp_index.device)
-            grad_sp, sp_index = _mask_padding(grad_sp, sp_index, saved[1])
-        if g_self is not None and (g_self.stride(1) != 1 or g_self.stride(0) < ctx.dim_origin):
-            g_self = g_self.contiguous()
-        grad_x = ops.maxk_backward(grad_sp, sp_index, dim_origin=ctx.dim_origin,
-                                   dropout=ctx.dropout, grad_dense=g_self)
-        if len(saved) == 2 and g_self is not None:
-            # a row that fills no slot (a constant row) has no last filled slot to point at:
-            # its slots stay (selector 0, gradient 0), which is harmless without g_self, but
-            # the merge would add g_self[r, 0] into a feature 0 that was not selected
-            grad_x.masked_fill_((saved[1] == 0)[:, None], 0.0)
+            grad_sp = ctx.plan.backward(g_agg.contiguous(), saved[0])
+        grad_x = _maxk_input_grad(grad_sp, saved[0], saved[1] if len(saved) == 2 else None,
+                                  ctx.dim_origin, ctx.dropout, g_self)
         return grad_x, None, None, None, None
 
 
@@ -559,29 +559,18 @@ class EdgeWeightedFunction(torch.autograd.Function):
         k = feat.shape[1] if form == "spgemm" else k
         plan = graph.weighted_plan(d, k)
         plan.refresh_values(val)
-        x_m, extra = None, ()
+        x_m = count = None
         if form == "spgemm":
             sp_data = feat
             out, _ = ops.spgemm_forward(graph.ptr, graph.idx, val, sp_data, sp_index,
                                         graph.num_nodes, graph.num_edges, k, d, plan=plan)
         else:
-            stats = torch.empty(2, dtype=torch.int32, device=feat.device) if plan.fwd_fixed else None
-            st2 = stats.view(1, 2) if stats is not None else None
             x_m = torch.empty_like(feat) if form == "self" else None
-            rec = plan.new_records()
-            if rec is not None:
-                res = ops.maxk_forward(feat, k, mode=mode, return_index=True, records=rec,
-                                       return_values=need_val, stats=stats,
-                                       return_count=mode != "exact", dropout=dropout, dense=x_m)
-                out = plan.forward_records(rec[0], rec[1], stats=st2)
-            else:
-                res = ops.maxk_forward(feat, k, mode=mode, return_index=True, out=plan.new_cbsr(),
-                                       stats=stats, return_count=mode != "exact",
-                                       dropout=dropout, dense=x_m)
-                out = plan.forward(res[0], res[1], stats=st2)
-            sp_data, sp_index, extra = res[0], res[1], res[2:]
-        ctx.save_for_backward(sp_index, *extra, *((sp_data,) if need_val else ()))
-        ctx.has_count, ctx.has_data = len(extra) == 1, need_val
+            out, sp_index, count, sp_data = _fused_forward(plan, feat, k, mode, dropout, x_m,
+                                                           need_val)
+        ctx.save_for_backward(sp_index, *(() if count is None else (count,)),
+                              *((sp_data,) if need_val else ()))
+        ctx.has_count, ctx.has_data = count is not None, need_val
         ctx.graph, ctx.plan, ctx.val = graph, plan, val
         ctx.form, ctx.dropout, ctx.dims = form, dropout, (d, k)
         ctx.set_materialize_grads(False)  # an unused output arrives as None, not as zeros
@@ -607,24 +596,12 @@ class EdgeWeightedFunction(torch.autograd.Function):
         if ctx.needs_input_grad[0] and (g_agg is not None or g_self is not None):
             grad_sp = None
             if g_agg is not None:
-                if plan._refs[2] is not val or plan.val_version != ops._version(val):
+                if ops._values_stale(plan, val):
                     plan.refresh_values(val)  # another weighted call ran on this graph since
                 grad_sp = plan.backward(g_agg, sp_index)
             if ctx.form == "spgemm":
                 return (grad_sp, grad_val) + none
-            # from here on as MaxKSelfAggregateFunction.backward (g_self None: the scatter of
-            # MaxKAggregateFunction)
-            if count is not None:
-                if grad_sp is None:
-                    grad_sp = torch.zeros(sp_index.shape, dtype=torch.float32,
-                                          device=sp_index.device)
-                grad_sp, sp_index = _mask_padding(grad_sp, sp_index, count)
-            if g_self is not None and (g_self.stride(1) != 1 or g_self.stride(0) < d):
-                g_self = g_self.contiguous()
-            grad_feat = ops.maxk_backward(grad_sp, sp_index, dim_origin=d, dropout=ctx.dropout,
-                                          grad_dense=g_self)
-            if count is not None and g_self is not None:
-                grad_feat.masked_fill_((count == 0)[:, None], 0.0)
+            grad_feat = _maxk_input_grad(grad_sp, sp_index, count, d, ctx.dropout, g_self)
         return (grad_feat, grad_val) + none
 
 

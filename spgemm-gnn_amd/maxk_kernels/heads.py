@@ -102,12 +102,9 @@ class HeadsAggregateFunction(torch.autograd.Function):
         alpha, sp_data, sp_index = ctx.saved_tensors  # read once
         graph = ctx.graph
         ptr_t, idx_t, _ = graph.transposed_structure()
-        if grad_out.dim() != 2 or grad_out.stride(1) != 1 or (
-                grad_out.shape[0] > 1 and grad_out.stride(0) < grad_out.shape[1]):
-            grad_out = grad_out.contiguous()  # strided rows are read in place
         grad_sp, grad_alpha = ops.heads_aggregate_backward(
-            ptr_t, idx_t, graph.transposed_order(), alpha, grad_out, sp_data, sp_index,
-            need_sp=need_sp, need_alpha=need_alpha)
+            ptr_t, idx_t, graph.transposed_order(), alpha, ops._rows_in_place(grad_out), sp_data,
+            sp_index, need_sp=need_sp, need_alpha=need_alpha)
         return None, grad_alpha, grad_sp, None, None
 
 

@@ -96,6 +96,14 @@ def _table(t: torch.Tensor, name: str, dtype: torch.dtype, rows: int, k: int) ->
     return t.stride(0) if rows > 1 else k
 
 
+def _rows_in_place(t: torch.Tensor) -> torch.Tensor:
+    """``t`` if :func:`_table` takes its rows as they are (2-D, unit column stride, row stride >=
+    the width; one row: any row stride), else a contiguous copy."""
+    if t.dim() != 2 or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        return t.contiguous()
+    return t
+
+
 def _records(buf, layout, rows: int, k: int, name: str) -> int:
     """A u8 [rows, record_bytes] buffer of forward records in chunk layout ``layout`` (1, 2 or
     4, ``maxk_plan_info.fwd_layout``); rows may be strided: returns the row stride in bytes."""
@@ -192,6 +200,9 @@ def maxk_forward(input: torch.Tensor, k: int, mode: str = "exact",
               "out must be on the input's device")
         ds = _table(sp_data, "out[0]", torch.float32, n, k)
         is_ = _table(sp_index, "out[1]", torch.uint8, n, k)
+    if not return_values:
+        sp_data = None  # neither written nor returned
+    values = _p(sp_data)
     count = torch.empty(n, dtype=torch.int32, device=input.device) if return_count else None
     scratch, sbytes = None, 0
     if stats is not None:
@@ -210,30 +221,21 @@ def maxk_forward(input: torch.Tensor, k: int, mode: str = "exact",
         if dense is not None:
             p, seed, row_offset = drop if drop is not None else (0.0, 0, 0)
             check(lib.maxk_topk_cbsr_dense(_p(input), _p(dense), dstride, _p(buf), rb, int(layout),
-                                           _p(sp_data if return_values else None), ds,
-                                           _p(sp_index), is_, _p(count), _p(stats), _p(scratch),
-                                           sbytes, n, d, k, TOPK_MODES[mode], p, seed, row_offset,
-                                           _stream()), "maxk_forward")
-            if not return_values:
-                sp_data = None
+                                           values, ds, _p(sp_index), is_, _p(count), _p(stats),
+                                           _p(scratch), sbytes, n, d, k, TOPK_MODES[mode], p,
+                                           seed, row_offset, _stream()), "maxk_forward")
         elif drop is not None:
-            check(lib.maxk_topk_cbsr_dropout(_p(input), _p(buf), rb, int(layout),
-                                             _p(sp_data if return_values else None), ds,
+            check(lib.maxk_topk_cbsr_dropout(_p(input), _p(buf), rb, int(layout), values, ds,
                                              _p(sp_index), is_, _p(count), _p(stats), _p(scratch),
                                              sbytes, n, d, k, TOPK_MODES[mode], drop[0], drop[1],
                                              drop[2], _stream()), "maxk_forward")
-            if not return_values:
-                sp_data = None
         elif records is not None:
-            check(lib.maxk_topk_cbsr_records(_p(input), _p(buf), rb, int(layout),
-                                             _p(sp_data if return_values else None), ds,
+            check(lib.maxk_topk_cbsr_records(_p(input), _p(buf), rb, int(layout), values, ds,
                                              _p(sp_index), is_, _p(count), _p(stats), _p(scratch),
                                              sbytes, n, d, k, TOPK_MODES[mode], _stream()),
                   "maxk_forward")
-            if not return_values:
-                sp_data = None
         else:
-            check(lib.maxk_topk_cbsr_ex(_p(input), _p(sp_data), ds, _p(sp_index), is_, _p(count),
+            check(lib.maxk_topk_cbsr_ex(_p(input), values, ds, _p(sp_index), is_, _p(count),
                                         _p(stats), _p(scratch), sbytes, n, d, k,
                                         TOPK_MODES[mode], _stream()), "maxk_forward")
     res = (sp_data, sp_index) if return_index else (sp_data,)
@@ -609,6 +611,12 @@ def _cache_budget(device) -> int:
     return torch.cuda.get_device_properties(device).total_memory // 4
 
 
+def _values_stale(plan, val) -> bool:
+    """Whether ``plan``'s value snapshot is of another tensor than ``val``, or of ``val`` before
+    an in-place edit: a ``refresh_values(val)`` is due."""
+    return plan._refs[2] is not val or plan.val_version != _version(val)
+
+
 def get_plan(ptr, idx, val, num_nodes, num_edges, dim_origin, dim_k) -> GraphPlan:
     """Cached plan for (graph storage, structure version, value tensor, k, D); in-place
     edits of ``val`` (a new ``val._version``) refresh the plan's value snapshot.
@@ -625,7 +633,7 @@ def get_plan(ptr, idx, val, num_nodes, num_edges, dim_origin, dim_k) -> GraphPla
         plan = _PLAN_CACHE.get(key)
         if plan is not None:
             _PLAN_CACHE.move_to_end(key)
-            if plan._refs[2] is not val or plan.val_version != _version(val):
+            if _values_stale(plan, val):
                 plan.refresh_values(val)
             return plan
         plan = GraphPlan(ptr, idx, val, int(num_nodes), int(num_edges), int(dim_origin),
@@ -661,6 +669,26 @@ def _check_graph(ptr, idx, val, num_nodes, num_edges):
 # -------------------------------------------------------------------------------------
 # SpGEMM forward / SSpMM backward
 # -------------------------------------------------------------------------------------
+def _resolve_plan(plan, ptr, idx, val, num_nodes, num_edges, dim_k, dim_origin, tables):
+    """The argument checks of :func:`spgemm_forward` and :func:`spgemm_backward`, and the plan
+    they run on: the caller's, or the cached one. ``tables``: ``(tensor, name, dtype, shape,
+    message for another shape)`` per table argument. The graph is checked unless it is the
+    plan's own, whose tensors were checked when it was built."""
+    if plan is None or plan._refs[0] is not ptr or plan._refs[1] is not idx or plan._refs[2] is not val:
+        _check_graph(ptr, idx, val, num_nodes, num_edges)
+    for t, name, dtype, _, _ in tables:
+        _check_tensor(t, name, dtype)
+    for t, _, _, shape, message in tables:
+        _need(t.shape == shape, message)
+    _need(1 <= dim_k <= dim_origin <= 256, "k must be between 1 and input dimension")
+    if plan is None:
+        plan = get_plan(ptr, idx, val, num_nodes, num_edges, dim_origin, dim_k)
+    _need(plan.num_rows == num_nodes and plan.num_edges == num_edges and
+          plan.dim_k == dim_k and plan.dim_origin == dim_origin,
+          "plan was built for a different graph / k / D")
+    return plan
+
+
 def spgemm_forward(ptr, idx, val, sp_data, sp_index, num_nodes: int, num_edges: int,
                    dim_k: int, dim_origin: int, plan: Optional[GraphPlan] = None
                    ) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -671,18 +699,10 @@ def spgemm_forward(ptr, idx, val, sp_data, sp_index, num_nodes: int, num_edges: 
     SO@0x221a0; checks bindings.cpp:45-54): ``out[r] = sum_nz val[nz] *
     densify(sp_data[idx[nz]], sp_index[idx[nz]])``.
     """
-    if plan is None or plan._refs[0] is not ptr or plan._refs[1] is not idx or plan._refs[2] is not val:
-        _check_graph(ptr, idx, val, num_nodes, num_edges)  # (a plan's own tensors were checked)
-    _check_tensor(sp_data, "sp_data", torch.float32)
-    _check_tensor(sp_index, "sp_index", torch.uint8)
-    _need(sp_data.shape == (num_nodes, dim_k) and sp_index.shape == (num_nodes, dim_k),
-          "sp_data and sp_index must be [num_nodes, dim_k]")
-    _need(1 <= dim_k <= dim_origin <= 256, "k must be between 1 and input dimension")
-    if plan is None:
-        plan = get_plan(ptr, idx, val, num_nodes, num_edges, dim_origin, dim_k)
-    _need(plan.num_rows == num_nodes and plan.num_edges == num_edges and
-          plan.dim_k == dim_k and plan.dim_origin == dim_origin,
-          "plan was built for a different graph / k / D")
+    shape, message = (num_nodes, dim_k), "sp_data and sp_index must be [num_nodes, dim_k]"
+    plan = _resolve_plan(plan, ptr, idx, val, num_nodes, num_edges, dim_k, dim_origin,
+                         ((sp_data, "sp_data", torch.float32, shape, message),
+                          (sp_index, "sp_index", torch.uint8, shape, message)))
     with _device(sp_data.device):
         out = plan.forward(sp_data, sp_index)
     return out, sp_index
@@ -697,18 +717,11 @@ def spgemm_backward(ptr, idx, val, grad_output, sp_index, num_nodes: int, num_ed
     num_edges, dim_k, dim_origin) -> [num_nodes, dim_k]`` (spgemm_backward_cuda
     SO@0x22490; checks bindings.cpp:65-71).
     """
-    if plan is None or plan._refs[0] is not ptr or plan._refs[1] is not idx or plan._refs[2] is not val:
-        _check_graph(ptr, idx, val, num_nodes, num_edges)
-    _check_tensor(grad_output, "grad_output", torch.float32)
-    _check_tensor(sp_index, "sp_index", torch.uint8)
-    _need(grad_output.shape == (num_nodes, dim_origin), "grad_output must be [num_nodes, dim_origin]")
-    _need(sp_index.shape == (num_nodes, dim_k), "sp_index must be [num_nodes, dim_k]")
-    _need(1 <= dim_k <= dim_origin <= 256, "k must be between 1 and input dimension")
-    if plan is None:
-        plan = get_plan(ptr, idx, val, num_nodes, num_edges, dim_origin, dim_k)
-    _need(plan.num_rows == num_nodes and plan.num_edges == num_edges and
-          plan.dim_k == dim_k and plan.dim_origin == dim_origin,
-          "plan was built for a different graph / k / D")
+    plan = _resolve_plan(plan, ptr, idx, val, num_nodes, num_edges, dim_k, dim_origin,
+                         ((grad_output, "grad_output", torch.float32, (num_nodes, dim_origin),
+                           "grad_output must be [num_nodes, dim_origin]"),
+                          (sp_index, "sp_index", torch.uint8, (num_nodes, dim_k),
+                           "sp_index must be [num_nodes, dim_k]")))
     with _device(grad_output.device):
         grad_sp = plan.backward(grad_output, sp_index)
     return grad_sp

@@ -42,13 +42,6 @@ def _check_rows(graph: CSRGraph) -> None:
                            f"{ops.MAX_ROW_EDGES}")
 
 
-def _rows_in_place(t: torch.Tensor) -> torch.Tensor:
-    """``t`` if its rows can be read in place (unit column stride, row stride >= width)."""
-    if t.dim() != 2 or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
-        return t.contiguous()
-    return t
-
-
 class MaxAggregateFunction(torch.autograd.Function):
     """``(out, arg_edge, arg_slot)`` from the CBSR tables on a CSRGraph. Saved: ``arg_edge``,
     ``arg_slot``, ``sp_index``. ``with_arg=False`` (no gradient will be asked for, and the caller
@@ -59,7 +52,7 @@ class MaxAggregateFunction(torch.autograd.Function):
     def forward(ctx, graph: CSRGraph, sp_data: torch.Tensor, sp_index: torch.Tensor,
                 dim_origin: int, with_arg: bool):
         out, arg_edge, arg_slot = ops.max_aggregate_forward(
-            graph.ptr, graph.idx, _rows_in_place(sp_data), sp_index, dim_origin, with_arg)
+            graph.ptr, graph.idx, ops._rows_in_place(sp_data), sp_index, dim_origin, with_arg)
         if not with_arg:
             arg_edge = torch.empty((0,), dtype=torch.int32, device=out.device)
             arg_slot = torch.empty((0,), dtype=torch.uint8, device=out.device)
@@ -81,7 +74,7 @@ class MaxAggregateFunction(torch.autograd.Function):
         graph = ctx.graph
         ptr_t, idx_t, _ = graph.transposed_structure()
         grad_sp = ops.max_aggregate_backward(ptr_t, idx_t, graph.transposed_order(),
-                                             _rows_in_place(grad_out), arg_edge, arg_slot,
+                                             ops._rows_in_place(grad_out), arg_edge, arg_slot,
                                              sp_index)
         return None, grad_sp, None, None, None
 
@@ -150,7 +143,7 @@ def max_aggregate_op(ptr: torch.Tensor, idx: torch.Tensor, ptr_t: torch.Tensor,
                      ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """``ops.max_aggregate_forward`` with the winners; the transposed structure ``(ptr_t, idx_t,
     order)``, int32, is read by the derivative only."""
-    return ops.max_aggregate_forward(ptr, idx, _rows_in_place(sp_data), sp_index, dim_origin,
+    return ops.max_aggregate_forward(ptr, idx, ops._rows_in_place(sp_data), sp_index, dim_origin,
                                      True)
 
 
@@ -166,7 +159,7 @@ def max_aggregate_backward_op(ptr_t: torch.Tensor, idx_t: torch.Tensor, order: t
                               grad_out: torch.Tensor, arg_edge: torch.Tensor,
                               arg_slot: torch.Tensor, sp_index: torch.Tensor) -> torch.Tensor:
     """``grad_sp [num_cols, k]`` (ops.max_aggregate_backward)."""
-    return ops.max_aggregate_backward(ptr_t, idx_t, order, _rows_in_place(grad_out), arg_edge,
+    return ops.max_aggregate_backward(ptr_t, idx_t, order, ops._rows_in_place(grad_out), arg_edge,
                                       arg_slot, sp_index)
 
 

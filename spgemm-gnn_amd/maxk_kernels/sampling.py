@@ -103,13 +103,6 @@ class Block(CSRGraph):
         """A^T, ``num_src`` rows over ``num_dst`` columns."""
         return Block(ptr_t, idx_t, val_t, num_src=self.num_dst)
 
-    def _transpose_order(self):
-        """``(ptr_t, idx_t, order)`` of A^T over ``num_src`` columns: ``CSRGraph._transpose``, the
-        HIP transposition on the GPU and the torch sort on CPU tensors. ``out_degrees``,
-        ``transposed``, ``transposed_structure`` and ``transposed_order`` are the inherited ones
-        on top of it."""
-        return self._transpose()
-
     def with_values(self, kind: str) -> "Block":
         key = ("graph", kind)
         g = self._values.get(key)

@@ -63,7 +63,7 @@ class Subgraph(CSRGraph):
             plan = ops.GraphPlan(self.ptr, self.idx, self.val, self.num_nodes, self.num_edges,
                                  int(dim_origin), int(dim_k))
             self._values[key] = (plan, structure)
-        elif plan._refs[2] is not self.val or plan.val_version != ops._version(self.val):
+        elif ops._values_stale(plan, self.val):
             plan.refresh_values(self.val)
         return plan
 

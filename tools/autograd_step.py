@@ -88,6 +88,7 @@ def dropout_report(args, graph, x, g, d, k, step_dropout, step_composed):
     t_fused = timeit(step_dropout)
     t_comp2 = timeit(step_composed)
     t_fused2 = timeit(step_dropout)
+    t_host = host_time(step_dropout)
     mem_fused, mem_comp = peak_bytes(step_dropout), peak_bytes(step_composed)
     plan = graph.plan(d, k)
     fixed = plan.fwd_fixed
@@ -125,6 +126,7 @@ def dropout_report(args, graph, x, g, d, k, step_dropout, step_composed):
                       "step_ms_fused_dropout": t_fused, "step_ms_fused_dropout_again": t_fused2,
                       "step_ms_composed": [t_comp1, t_comp2],
                       "fused_not_slower": t_fused <= max(t_comp1, t_comp2),
+                      "host_ms_per_step_fused_dropout": t_host,
                       "peak_bytes_fused": mem_fused, "peak_bytes_composed": mem_comp,
                       "peak_bytes_saved": mem_comp - mem_fused, "kernels": kern}), flush=True)
 
@@ -180,6 +182,7 @@ def self_report(args, graph, x, g, g_self, d, k, step_self, step_self_composed):
     t_fused = timeit(step_self)
     t_comp2 = timeit(step_self_composed)
     t_fused2 = timeit(step_self)
+    t_host = host_time(step_self)
     mem_fused, mem_comp = peak_bytes(step_self), peak_bytes(step_self_composed)
     plan = graph.plan(d, k)
     fixed = plan.fwd_fixed
@@ -223,6 +226,7 @@ def self_report(args, graph, x, g, g_self, d, k, step_self, step_self_composed):
                       "fused_not_slower": t_fused <= slower,
                       "speedup_vs_slower_composed": slower / t_fused,
                       "speedup_vs_faster_composed": min(t_comp1, t_comp2) / t_fused,
+                      "host_ms_per_step_self_fused": t_host,
                       "peak_bytes_fused": mem_fused, "peak_bytes_composed": mem_comp,
                       "peak_bytes_saved": mem_comp - mem_fused, "kernels": kern}), flush=True)
 
@@ -321,6 +325,7 @@ def main():
     t_unfused = timeit(step_unfused)
     t_fresh2 = timeit(step_fresh)   # again, after the unfused variant (order effects)
     t_host = host_time(step_fresh)
+    mem_fresh = peak_bytes(step_fresh)
     plan = graph.plan(d, k)
     sp_data, sp_index = mk.maxk_forward(x.detach(), k, return_index=True)
     out = torch.empty(n, d, device=dev)
@@ -360,7 +365,8 @@ def main():
                       "fwd_fixed": int(fixed),
                       "step_ms": t_step, "step_ms_grad_none": t_fresh,
                       "step_ms_grad_none_again": t_fresh2, "step_ms_unfused": t_unfused,
-                      "host_ms_per_step": t_host, "fused_parts": fused,
+                      "host_ms_per_step": t_host, "peak_bytes_grad_none": mem_fresh,
+                      "fused_parts": fused,
                       "parts": parts, "parts_sum_ms": sum(parts.values())}), flush=True)
 
 
