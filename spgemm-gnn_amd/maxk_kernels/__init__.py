@@ -64,6 +64,7 @@ from .heads import (  # noqa: F401,E402  (and its operators)
     heads_aggregate,
     maxk_heads_aggregate,
 )
+from .gatv2 import MaxKGATv2Conv, edge_softmax_heads, gatv2_attention  # noqa: F401,E402
 from .pooling import (  # noqa: F401,E402  (and its operators)
     MaxAggregateFunction,
     dense_max_aggregate,
@@ -108,6 +109,7 @@ __all__ = [
     "MaxKGATConv", "gat_attention", "GATAttentionFunction",
     "gat_attention_heads", "GATAttentionHeadsFunction", "heads_aggregate", "maxk_heads_aggregate",
     "HeadsAggregateFunction", "heads_row_limits",
+    "edge_softmax_heads", "gatv2_attention", "MaxKGATv2Conv",
     "max_aggregate", "maxk_max_aggregate", "dense_max_aggregate", "MaxAggregateFunction",
     "max_row_limits",
     "sample_neighbors", "block_compact", "Block", "to_block", "NeighborSampler", "layer_seed",

@@ -104,6 +104,21 @@ SIGNATURES = {
                                                      _i64, _vp, _vp, _i32, _i32, _i32, _i64, _i32,
                                                      _i32, _vp]),
     "maxk_heads_row_limits": (ctypes.c_int, [_vp, _i32]),
+    "maxk_gatv2_score_forward": (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp,
+                                                ctypes.c_float, _vp, _i32, _i32, _i32, _i64, _i32,
+                                                _i32, _vp]),
+    "maxk_edge_softmax_forward_heads": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i64, _vp]),
+    "maxk_edge_softmax_backward_heads": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i64,
+                                                        _vp]),
+    "maxk_gatv2_score_backward_rows": (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64,
+                                                      _vp, ctypes.c_float, _vp, _vp, _vp, _vp,
+                                                      _i64, _i32, _i32, _i32, _i64, _i32, _i32,
+                                                      _vp]),
+    "maxk_gatv2_score_backward_cols": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp,
+                                                      _i64, _vp, ctypes.c_float, _vp, _vp, _i32,
+                                                      _i32, _i32, _i64, _i32, _i32, _vp]),
+    "maxk_gatv2_scratch_bytes": (ctypes.c_int64, [_i32, _i32]),
+    "maxk_gatv2_row_limits": (ctypes.c_int, [_vp, _i32]),
     "maxk_max_aggregate_forward": (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp,
                                                   _i32, _i32, _i64, _i32, _i32, _vp]),
     "maxk_max_aggregate_backward": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64,

@@ -1089,6 +1089,135 @@ def heads_row_limits() -> Tuple[int, ...]:
 
 
 # -------------------------------------------------------------------------------------
+# MaxK GATv2 attention (include/maxk_hip.h, "MaxK GATv2 attention")
+# -------------------------------------------------------------------------------------
+def _gatv2_args(sp_data, sp_index, fd, attn, dev):
+    """The tables ``[num_cols, k]``, ``fd`` f32 ``[num_rows, D]`` (rows may be strided) and
+    ``attn`` f32 ``[H, F]`` with ``H * F == D``: ``(H, num_rows, num_cols, D, k, ds, is, fs)``."""
+    num_cols, k, ds, is_ = _heads_tables(sp_data, sp_index, dev)
+    _need(isinstance(fd, torch.Tensor) and fd.dim() == 2, "fd must be [num_rows, dim_origin]")
+    n, d = fd.shape
+    fs = _table(fd, "fd", torch.float32, n, d)
+    _matrix(attn, "attn", None, None, "num_heads, dim_origin / num_heads", dev)
+    _need(fd.device == dev and attn.numel() == d and attn.shape[0] >= 1,
+          "attn must be [num_heads, dim_origin / num_heads] on fd's device")
+    _need(1 <= k <= d <= 256, "k must be between 1 and input dimension")
+    return attn.shape[0], n, num_cols, d, k, ds, is_, fs
+
+
+def gatv2_score(ptr, idx, sp_data, sp_index, fd, attn, negative_slope: float,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The GATv2 logits of MaxK features, f32 ``[H, num_edges]`` head-major: ``sum_l attn[s] *
+    (lrelu(sp_data[u, l] + fd[v, s]) - lrelu(fd[v, s]))`` over the slots of edge ``u -> v`` whose
+    feature ``s = sp_index[u, l]`` lies in the head (``maxk_gatv2_score_forward``; include/
+    maxk_hip.h, "MaxK GATv2 attention")."""
+    _check_ptr(ptr, "ptr", "num_rows")
+    dev = ptr.device
+    _vector(idx, "idx", torch.int32, None, "num_edges", dev)
+    h, n, num_cols, d, k, ds, is_, fs = _gatv2_args(sp_data, sp_index, fd, attn, dev)
+    _need(n == ptr.numel() - 1, "fd must have num_rows rows")
+    e = idx.numel()
+    out = _out_matrix(out, "out", h, e, "num_heads, num_edges", dev)
+    with _device(dev):
+        check(lib.maxk_gatv2_score_forward(_p(ptr), _p(idx), _p(sp_data), ds, _p(sp_index), is_,
+                                           _p(fd), fs, _p(attn), float(negative_slope), _p(out),
+                                           h, n, num_cols, e, d, k, _stream()), "gatv2_score")
+    return out
+
+
+def _softmax_heads_args(ptr, tensors, names, out):
+    _check_ptr(ptr, "ptr", "num_rows")
+    dev = ptr.device
+    h = e = None
+    for t, name in zip(tensors, names):
+        _matrix(t, name, h, e, "num_heads, num_edges", dev)
+        h, e = t.shape
+    _need(h >= 1, "logits must have at least one head")
+    return ptr.numel() - 1, h, e, _out_matrix(out, "out", h, e, "num_heads, num_edges", dev)
+
+
+def edge_softmax_heads(ptr, logits, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`edge_softmax` of every row of ``logits`` f32 ``[H, num_edges]`` in one launch; row
+    ``h`` is the single-head call bit for bit (``maxk_edge_softmax_forward_heads``)."""
+    n, h, e, out = _softmax_heads_args(ptr, (logits,), ("logits",), out)
+    with _device(ptr.device):
+        check(lib.maxk_edge_softmax_forward_heads(_p(ptr), _p(logits), _p(out), h, n, e,
+                                                  _stream()), "edge_softmax_heads")
+    return out
+
+
+def edge_softmax_backward_heads(ptr, y, grad_y, out: Optional[torch.Tensor] = None):
+    """:func:`edge_softmax_backward` of every row of ``y``, ``grad_y`` f32 ``[H, num_edges]``
+    (``maxk_edge_softmax_backward_heads``)."""
+    n, h, e, out = _softmax_heads_args(ptr, (y, grad_y), ("y", "grad_y"), out)
+    with _device(ptr.device):
+        check(lib.maxk_edge_softmax_backward_heads(_p(ptr), _p(y), _p(grad_y), _p(out), h, n, e,
+                                                   _stream()), "edge_softmax_backward_heads")
+    return out
+
+
+def gatv2_scratch_bytes(num_rows: int, dim_origin: int) -> int:
+    return int(lib.maxk_gatv2_scratch_bytes(int(num_rows), int(dim_origin)))
+
+
+def gatv2_score_backward_rows(ptr, idx, sp_data, sp_index, fd, attn, negative_slope: float,
+                              grad_logits, out=None, scratch=None):
+    """``(grad_fd [num_rows, D], grad_attn [H, F])`` of :func:`gatv2_score` from ``grad_logits``
+    f32 ``[H, num_edges]`` (``maxk_gatv2_score_backward_rows``). ``out=(grad_fd, grad_attn)``:
+    contiguous f32 tensors to write into; ``scratch``: a u8 tensor of at least
+    :func:`gatv2_scratch_bytes` bytes."""
+    _check_ptr(ptr, "ptr", "num_rows")
+    dev = ptr.device
+    _vector(idx, "idx", torch.int32, None, "num_edges", dev)
+    h, n, num_cols, d, k, ds, is_, fs = _gatv2_args(sp_data, sp_index, fd, attn, dev)
+    _need(n == ptr.numel() - 1, "fd must have num_rows rows")
+    e = idx.numel()
+    _matrix(grad_logits, "grad_logits", h, e, "num_heads, num_edges", dev)
+    grad_fd, grad_attn = out if out is not None else (None, None)
+    grad_fd = _out_matrix(grad_fd, "out[0]", n, d, "num_rows, dim_origin", dev)
+    grad_attn = _out_matrix(grad_attn, "out[1]", h, d // h, "num_heads, dim_origin / num_heads",
+                            dev)
+    nbytes = gatv2_scratch_bytes(n, d)
+    scratch = _scratch(scratch, nbytes, dev)
+    with _device(dev):
+        check(lib.maxk_gatv2_score_backward_rows(_p(ptr), _p(idx), _p(sp_data), ds, _p(sp_index),
+                                                 is_, _p(fd), fs, _p(attn), float(negative_slope),
+                                                 _p(grad_logits), _p(grad_fd), _p(grad_attn),
+                                                 _p(scratch), scratch.numel(), h, n, num_cols, e,
+                                                 d, k, _stream()), "gatv2_score_backward_rows")
+    return grad_fd, grad_attn
+
+
+def gatv2_score_backward_cols(ptr_t, idx_t, order, sp_data, sp_index, fd, attn,
+                              negative_slope: float, grad_logits,
+                              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``grad_sp [num_cols, k]`` of :func:`gatv2_score` over the transposed structure ``(ptr_t,
+    idx_t, order)``, all int32 (``maxk_gatv2_score_backward_cols``)."""
+    _check_ptr(ptr_t, "ptr_t", "num_cols")
+    dev = ptr_t.device
+    _vector(order, "order", torch.int32, None, "num_edges", dev)
+    e = order.numel()
+    _vector(idx_t, "idx_t", torch.int32, e, "num_edges", dev)
+    h, n, num_cols, d, k, ds, is_, fs = _gatv2_args(sp_data, sp_index, fd, attn, dev)
+    _need(num_cols == ptr_t.numel() - 1, "sp_data must have num_cols rows")
+    _matrix(grad_logits, "grad_logits", h, e, "num_heads, num_edges", dev)
+    out = _out_matrix(out, "out", num_cols, k, "num_cols, dim_k", dev)
+    with _device(dev):
+        check(lib.maxk_gatv2_score_backward_cols(_p(ptr_t), _p(idx_t), _p(order), _p(sp_data), ds,
+                                                 _p(sp_index), is_, _p(fd), fs, _p(attn),
+                                                 float(negative_slope), _p(grad_logits), _p(out),
+                                                 h, n, num_cols, e, d, k, _stream()),
+              "gatv2_score_backward_cols")
+    return out
+
+
+def gatv2_row_limits() -> Tuple[int, ...]:
+    """``(row_short, row_medium, col_short, col_medium)`` of the GATv2 score kernels
+    (``maxk_gatv2_row_limits``)."""
+    return _int32_list(lib.maxk_gatv2_row_limits)
+
+
+# -------------------------------------------------------------------------------------
 # Max aggregation (include/maxk_hip.h, "Max aggregation")
 # -------------------------------------------------------------------------------------
 MAX_ROW_EDGES = 1 << 24  # the forward's precondition: every row is shorter than this
