@@ -17,7 +17,10 @@ from ._lib import LIB_PATH, MaxKError, lib  # noqa: F401  (loads libmaxk_hip.so)
 from .ops import (  # noqa: F401
     TOPK_MODES,
     GraphPlan,
+    cbsr_matmul,
+    cbsr_sampled_matmul,
     cbsr_stats,
+    cbsr_weight_grad,
     csr_transpose,
     clear_plan_cache,
     dense_spmm,
@@ -64,6 +67,7 @@ from .heads import (  # noqa: F401,E402  (and its operators)
     heads_aggregate,
     maxk_heads_aggregate,
 )
+from .linear import CBSRMatmulFunction, LinearMaxKFunction, cbsr_linear, linear_maxk  # noqa: F401,E402
 from .gatv2 import MaxKGATv2Conv, edge_softmax_heads, gatv2_attention  # noqa: F401,E402
 from .pooling import (  # noqa: F401,E402  (and its operators)
     MaxAggregateFunction,
@@ -116,6 +120,8 @@ __all__ = [
     "block_aggregate", "block_self_aggregate", "block_spgemm", "sample_row_limits",
     "node_subgraph", "Subgraph", "random_partition", "ClusterLoader", "subgraph_row_limits",
     "csr_transpose", "transpose_digit_bits",
+    "cbsr_matmul", "cbsr_sampled_matmul", "cbsr_weight_grad", "cbsr_linear", "linear_maxk",
+    "CBSRMatmulFunction", "LinearMaxKFunction",
 ]
 
 ABI_VERSION = lib.maxk_abi_version()

@@ -56,6 +56,17 @@ per-call pack or statistics pass, no ``[N, k]`` value table saved). Training wit
 ``feat_drop > 0`` and ``fused_dropout=False`` keeps the composition ``maxk`` → ``F.dropout`` →
 ``densify`` / ``spgemm``, because it draws ``F.dropout``'s random numbers.
 
+``sparse_linear=True`` (``MaxKSAGEConv``, ``MaxKSAGE``, ``MaxKGCNConv``; default off) runs the weight
+products next to the MaxK on the CBSR tables (:mod:`maxk_kernels.linear`) instead of dense GEMMs on
+rows that are ``1 - k / D`` zeros. ``MaxKSAGEConv`` in its default ordering with the ``mean`` or
+``sum`` aggregator computes ``x = feat_drop(MaxK(feat))`` as CBSR once, aggregates it with
+``spgemm`` and takes the self term ``fc_self(x)`` from ``cbsr_linear``, so no dense masked row is
+built. ``MaxKGCNConv`` with its own ``weight`` takes ``MaxK(feat W)`` from ``linear_maxk``, whose
+backward never writes the ``[N, D]`` gradient of ``feat W`` and which needs ``topk_mode="exact"``.
+A sampled ``Block``, the other aggregators and orderings and ``nonlinear="relu"`` keep their
+present path. The options are off by default: measured, only the forward product is faster than
+the GEMM it replaces (README, "Measured results").
+
 ``norm`` of ``MaxKSAGEConv`` may be a module instance (DGL's convention) or a class that is
 instantiated as ``norm(out_feats)`` (utils/maxk_layers.py:66-67).
 
@@ -90,6 +101,7 @@ import torch.nn.functional as F
 from .autograd import (CSRGraph, dense_aggregate, densify, edge_softmax, maxk, maxk_aggregate,
                        maxk_self_aggregate, spgemm)
 from .attention import gat_attention
+from .linear import cbsr_linear, linear_maxk
 from .heads import gat_attention_heads, heads_aggregate, maxk_heads_aggregate
 from .pooling import dense_max_aggregate, maxk_max_aggregate
 from .sampling import Block, block_aggregate, block_self_aggregate, block_spgemm
@@ -172,9 +184,10 @@ class MaxKSAGEConv(nn.Module):
 
     def __init__(self, in_feats, out_feats, aggregator_type="mean", feat_drop=0., norm=None,
                  maxk=32, bias=True, maxk_after_fc=False, topk_mode="exact",
-                 nonlinear="maxk", fused_dropout=False):
+                 nonlinear="maxk", fused_dropout=False, sparse_linear=False):
         super().__init__()
         self.fused_dropout = bool(fused_dropout)
+        self.sparse_linear = bool(sparse_linear)
         if aggregator_type not in ("mean", "sum", "pool", "gcn"):
             raise ValueError(f"Unsupported aggregator type: {aggregator_type}")
         if maxk_after_fc and aggregator_type in ("pool", "gcn"):
@@ -302,6 +315,11 @@ class MaxKSAGEConv(nn.Module):
             else:  # no dropout between MaxK and the SpGEMM: the fused producer-consumer pair
                 rst = h_self + maxk_aggregate(self.fc_neigh(feat), csr, self.maxk, self.topk_mode,
                                               edge_weight=ew)
+        elif self.sparse_linear:
+            # the self term on the CBSR tables: no dense masked row
+            sp_data, sp_index = _maxk_dropout(self, feat)
+            neigh = spgemm(sp_data, sp_index, csr, self.in_feats, edge_weight=ew)
+            rst = cbsr_linear(sp_data, sp_index, self.fc_self.weight) + self.fc_neigh(neigh)
         else:
             x, neigh = _maxk_self_pair(self, feat, csr, ew)
             rst = self.fc_self(x) + self.fc_neigh(neigh)
@@ -319,9 +337,10 @@ class MaxKGCNConv(nn.Module):
 
     def __init__(self, in_feats, out_feats, norm="both", weight=True, bias=True,
                  allow_zero_in_degree=False, maxk=32, topk_mode="exact", feat_drop=0.,
-                 nonlinear="maxk", fused_dropout=False):
+                 nonlinear="maxk", fused_dropout=False, sparse_linear=False):
         super().__init__()
         self.fused_dropout = bool(fused_dropout)
+        self.sparse_linear = bool(sparse_linear)
         if norm not in ("both", "right", "left", "none"):
             raise ValueError(f"Invalid norm value {norm!r}")
         self.in_feats = in_feats
@@ -348,6 +367,13 @@ class MaxKGCNConv(nn.Module):
         csr = as_csr(graph, ew)
         if not self.allow_zero_in_degree and bool((csr.in_degrees() == 0).any()):
             raise ValueError("Graph has nodes with zero in-degree")
+        if self.sparse_linear and self.weight is not None and self.nonlinear == "maxk":
+            # MaxK(feat W) whose backward takes the [N, k] gradient as it is
+            sp_data, sp_index = linear_maxk(feat, self.weight.t(), None, self.maxk, self.topk_mode)
+            sp_data = _sparse_dropout(sp_data, self.feat_drop, self.training)
+            rst = spgemm(sp_data, sp_index, csr.with_values(self.norm), self.out_feats,
+                         edge_weight=ew)
+            return rst + self.bias if self.bias is not None else rst
         if self.weight is not None:
             feat = feat @ self.weight
         if self.nonlinear == "relu":
@@ -530,7 +556,8 @@ class MaxKSAGE(nn.Module):
     ``nonlinear='relu'`` the utils/models.py:109-165 SAGE: ReLU, then dglnn.SAGEConv(mean)."""
 
     def __init__(self, in_size, hid_size, num_hid_layers, out_size, maxk=32, feat_drop=0.5,
-                 norm=False, nonlinear="maxk", fused_dropout=False, aggregator_type="mean"):
+                 norm=False, nonlinear="maxk", fused_dropout=False, aggregator_type="mean",
+                 sparse_linear=False):
         super().__init__()
         self.nonlinear = _check_nonlinear(nonlinear)
         self.num_layers = num_hid_layers
@@ -539,7 +566,8 @@ class MaxKSAGE(nn.Module):
         self.layers = nn.ModuleList(
             MaxKSAGEConv(hid_size, hid_size, aggregator_type, feat_drop=feat_drop,
                          norm=nn.LayerNorm(hid_size) if norm else None, maxk=maxk,
-                         nonlinear=nonlinear, fused_dropout=fused_dropout)
+                         nonlinear=nonlinear, fused_dropout=fused_dropout,
+                         sparse_linear=sparse_linear)
             for _ in range(num_hid_layers))
         nn.init.xavier_uniform_(self.lin_in.weight)
         nn.init.xavier_uniform_(self.lin_out.weight)

@@ -1,0 +1,94 @@
+"""The weight products on either side of a MaxK, on the CBSR tables instead of dense rows.
+
+A node keeps ``k`` of ``D`` features, so a linear layer that reads the MaxK output, and the
+backward of one that feeds it, are products of ``N k M`` multiply-adds, where the dense GEMMs on
+the masked rows are ``N D M`` on operands that are ``1 - k / D`` zeros. The three kernels are
+``ops.cbsr_matmul`` (A), ``ops.cbsr_sampled_matmul`` (B) and ``ops.cbsr_weight_grad`` (C)
+(include/maxk_hip.h, "MaxK linear layers"):
+
+* :func:`cbsr_linear` is ``densify(sp) @ weight.T + bias`` without the dense row: forward (A),
+  backward (B) for the kept values and (C) for the weight.
+* :func:`linear_maxk` is ``maxk(F.linear(h, weight, bias), k)`` whose backward takes the gradient
+  of the kept values as it is: ``grad_h`` by (A) with ``weight`` as the table, ``grad_weight`` and
+  ``grad_bias`` by (C) with ``h`` in the place of the gradient. No ``[N, D]`` gradient is written.
+
+Both are first order only, as every Function of :mod:`maxk_kernels.autograd`.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+import torch.nn.functional as F
+
+from . import ops
+from .autograd import first_order_only
+
+
+class CBSRMatmulFunction(torch.autograd.Function):
+    """``(sp_data, sp_index, table [D, M], bias) -> densify(sp) @ table + bias``."""
+
+    @staticmethod
+    def forward(ctx, sp_data, sp_index, table, bias):
+        sp_data, table = ops._rows_in_place(sp_data), ops._rows_in_place(table)
+        ctx.save_for_backward(sp_data, sp_index, table)
+        return ops.cbsr_matmul(sp_data, sp_index, table,
+                               None if bias is None else bias.contiguous())
+
+    @staticmethod
+    @first_order_only
+    def backward(ctx, grad_out):
+        sp_data, sp_index, table = ctx.saved_tensors
+        g = ops._rows_in_place(grad_out)
+        need = ctx.needs_input_grad
+        grad_data = ops.cbsr_sampled_matmul(g, sp_index, table) if need[0] else None
+        grad_table = (ops.cbsr_weight_grad(sp_data, sp_index, g, table.shape[0])
+                      if need[2] else None)
+        return grad_data, None, grad_table, g.sum(0) if need[3] else None
+
+
+def cbsr_linear(sp_data: torch.Tensor, sp_index: torch.Tensor, weight: torch.Tensor,
+                bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``densify(sp_data, sp_index, D) @ weight.T + bias`` as ``[N, M]`` for ``weight [M, D]``
+    (``nn.Linear``'s layout), differentiable in ``sp_data``, ``weight`` and ``bias``. The table of
+    the kernels is ``weight.t()`` made contiguous by torch, ``[D, M]`` (at most 256 KB)."""
+    return CBSRMatmulFunction.apply(sp_data, sp_index, weight.t().contiguous(), bias)
+
+
+class LinearMaxKFunction(torch.autograd.Function):
+    """``(h, weight [D, D_in], bias) -> maxk(h @ weight.T + bias, k)`` in exact mode; only ``h``
+    and the selectors are saved."""
+
+    @staticmethod
+    def forward(ctx, h, weight, bias, k):
+        sp_data, sp_index = ops.maxk_forward(F.linear(h, weight, bias), k, mode="exact",
+                                             return_index=True)
+        ctx.save_for_backward(h, weight, sp_index)
+        ctx.mark_non_differentiable(sp_index)
+        return sp_data, sp_index
+
+    @staticmethod
+    @first_order_only
+    def backward(ctx, grad_data, grad_index):
+        h, weight, sp_index = ctx.saved_tensors
+        grad_data = ops._rows_in_place(grad_data)
+        need = ctx.needs_input_grad
+        grad_h = grad_w = grad_b = None
+        if need[0]:
+            grad_h = ops.cbsr_matmul(grad_data, sp_index, ops._rows_in_place(weight))
+        if need[1] or need[2]:
+            res = ops.cbsr_weight_grad(grad_data, sp_index, ops._rows_in_place(h),
+                                       weight.shape[0], with_sum=bool(need[2]))
+            grad_w, grad_b = res if need[2] else (res, None)
+        return grad_h, grad_w if need[1] else None, grad_b, None
+
+
+def linear_maxk(h: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], k: int,
+                mode: str = "exact"):
+    """``(sp_data, sp_index) = maxk(F.linear(h, weight, bias), k)`` for ``weight [D, D_in]``,
+    differentiable in ``h``, ``weight`` and ``bias``. ``mode="ref_compat"`` is refused: its padding
+    slots carry no gradient, which takes the rule of the scatter (``autograd._mask_padding``)."""
+    if mode != "exact":
+        raise ValueError(f'linear_maxk supports mode="exact" only, got {mode!r}: the padding '
+                         "slots of ref_compat need the MaxK scatter's rule")
+    return LinearMaxKFunction.apply(h, weight, bias, k)

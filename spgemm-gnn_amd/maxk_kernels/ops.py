@@ -1218,6 +1218,104 @@ def gatv2_row_limits() -> Tuple[int, ...]:
 
 
 # -------------------------------------------------------------------------------------
+# MaxK linear layers (include/maxk_hip.h, "MaxK linear layers"): CBSR times a [D, M] table
+# -------------------------------------------------------------------------------------
+CBSR_MATMUL, CBSR_SAMPLED_MATMUL, CBSR_WEIGHT_GRAD = 0, 1, 2
+
+
+def cbsr_linear_scratch_bytes(op: int, num_rows: int, dim_origin: int, dim_k: int,
+                              dim_m: int) -> int:
+    return int(lib.maxk_cbsr_linear_scratch_bytes(int(op), int(num_rows), int(dim_origin),
+                                                  int(dim_k), int(dim_m)))
+
+
+def cbsr_linear_panel(dim_origin: int, dim_m: int) -> Tuple[int, ...]:
+    """``(panel width, panels)`` of the kernels for a ``[dim_origin, dim_m]`` table
+    (``maxk_cbsr_linear_panel``)."""
+    return _int32_list(lib.maxk_cbsr_linear_panel, int(dim_origin), int(dim_m))
+
+
+def _rows(t, name: str, rows, cols, shape_name: str, dev):
+    """An f32 ``[rows, cols]`` tensor (``None``: any extent) on ``dev`` whose rows may be strided:
+    ``(rows, cols, row stride)``."""
+    _need(isinstance(t, torch.Tensor) and t.dim() == 2 and
+          (rows is None or t.shape[0] == rows) and (cols is None or t.shape[1] == cols),
+          f"{name} must be [{shape_name}]")
+    _need(t.device == dev, "all tensors must be on the same device")
+    return t.shape[0], t.shape[1], _table(t, name, torch.float32, t.shape[0], t.shape[1])
+
+
+def cbsr_matmul(sp_data, sp_index, table, bias=None, out=None) -> torch.Tensor:
+    """``densify(sp_data, sp_index) @ table (+ bias)``: f32 ``[N, M]`` from the CBSR tables
+    ``[N, k]`` and ``table`` f32 ``[D, M]`` (``maxk_cbsr_matmul``). Rows of every 2-D argument
+    may be strided."""
+    dev = sp_data.device if isinstance(sp_data, torch.Tensor) else None
+    n, k, ds, is_ = _heads_tables(sp_data, sp_index, dev)
+    d, m, ts = _rows(table, "table", None, None, "dim_origin, dim_m", dev)
+    _need(1 <= k <= d <= 256 and m >= 1, "k must be between 1 and input dimension")
+    if bias is not None:
+        _vector(bias, "bias", torch.float32, m, "dim_m", dev)
+    if out is None:
+        out = torch.empty((n, m), dtype=torch.float32, device=dev)
+    os_ = _rows(out, "out", n, m, "num_rows, dim_m", dev)[2]
+    with _device(dev):
+        check(lib.maxk_cbsr_matmul(_p(sp_data), ds, _p(sp_index), is_, _p(table), ts, _p(bias),
+                                   _p(out), os_, n, d, k, m, _stream()), "cbsr_matmul")
+    return out
+
+
+def cbsr_sampled_matmul(g, sp_index, table, out=None, scratch=None) -> torch.Tensor:
+    """``out[n, l] = <g[n, :], table[sp_index[n, l], :]>``: f32 ``[N, k]`` from ``g`` f32
+    ``[N, M]``, the selectors u8 ``[N, k]`` and ``table`` f32 ``[D, M]``
+    (``maxk_cbsr_sampled_matmul``); ``scratch``: a u8 tensor of at least
+    :func:`cbsr_linear_scratch_bytes` bytes."""
+    _need(isinstance(sp_index, torch.Tensor) and sp_index.dim() == 2,
+          "sp_index must be [num_rows, dim_k]")
+    dev = sp_index.device
+    n, k = sp_index.shape
+    is_ = _table(sp_index, "sp_index", torch.uint8, n, k)
+    d, m, ts = _rows(table, "table", None, None, "dim_origin, dim_m", dev)
+    _need(1 <= k <= d <= 256 and m >= 1, "k must be between 1 and input dimension")
+    gs = _rows(g, "g", n, m, "num_rows, dim_m", dev)[2]
+    if out is None:
+        out = torch.empty((n, k), dtype=torch.float32, device=dev)
+    os_ = _rows(out, "out", n, k, "num_rows, dim_k", dev)[2]
+    scratch = _scratch(scratch, cbsr_linear_scratch_bytes(CBSR_SAMPLED_MATMUL, n, d, k, m), dev)
+    with _device(dev):
+        check(lib.maxk_cbsr_sampled_matmul(_p(g), gs, _p(sp_index), is_, _p(table), ts, _p(out),
+                                           os_, _p(scratch), scratch.numel(), n, d, k, m,
+                                           _stream()), "cbsr_sampled_matmul")
+    return out
+
+
+def cbsr_weight_grad(sp_data, sp_index, g, dim_origin: int, with_sum: bool = False, out=None,
+                     scratch=None):
+    """``densify(sp_data, sp_index).T @ g``: f32 ``[D, M]`` from the CBSR tables ``[N, k]`` and
+    ``g`` f32 ``[N, M]``; with ``with_sum`` also the column sums of ``densify``, f32 ``[D]``, as
+    ``(grad_table, grad_sum)`` (``maxk_cbsr_weight_grad``). ``out``: the tensor(s) to write into;
+    ``scratch``: a u8 tensor of at least :func:`cbsr_linear_scratch_bytes` bytes."""
+    dev = sp_data.device if isinstance(sp_data, torch.Tensor) else None
+    n, k, ds, is_ = _heads_tables(sp_data, sp_index, dev)
+    d = int(dim_origin)
+    _need(1 <= k <= d <= 256, "k must be between 1 and input dimension")
+    m, gs = _rows(g, "g", n, None, "num_rows, dim_m", dev)[1:]
+    _need(m >= 1, "g must have at least one column")
+    grad_table, grad_sum = (out if with_sum else (out, None)) if out is not None else (None, None)
+    if grad_table is None:
+        grad_table = torch.empty((d, m), dtype=torch.float32, device=dev)
+    dts = _rows(grad_table, "out", d, m, "dim_origin, dim_m", dev)[2]
+    if with_sum:
+        grad_sum = _out_vector(grad_sum, "out[1]", d, "dim_origin", dev)
+    scratch = _scratch(scratch, cbsr_linear_scratch_bytes(CBSR_WEIGHT_GRAD, n, d, k, m), dev)
+    with _device(dev):
+        check(lib.maxk_cbsr_weight_grad(_p(sp_data), ds, _p(sp_index), is_, _p(g), gs,
+                                        _p(grad_table), dts, _p(grad_sum), _p(scratch),
+                                        scratch.numel(), n, d, k, m, _stream()),
+              "cbsr_weight_grad")
+    return (grad_table, grad_sum) if with_sum else grad_table
+
+
+# -------------------------------------------------------------------------------------
 # Max aggregation (include/maxk_hip.h, "Max aggregation")
 # -------------------------------------------------------------------------------------
 MAX_ROW_EDGES = 1 << 24  # the forward's precondition: every row is shorter than this

@@ -13,6 +13,13 @@
 // does the same for the tables of csrc/variants_transpose.h alone (the transposition's passes over
 // every pass count, and its digit plan over every key width); their names are the pass kernels of
 // tests/golden/kernel_instantiations_transpose.txt.
+//
+//   variant_check linear
+//
+// does it for the tables of csrc/variants_linear.h (the panel kernels of the CBSR-times-table
+// products over every D and the widths of M around the panel edges, with the panel cover and the
+// scratch sizes); their names are the panel kernels of
+// tests/golden/kernel_instantiations_linear.txt.
 #include <algorithm>
 #include <climits>
 #include <cstdio>
@@ -21,6 +28,7 @@
 #include <vector>
 
 #include "variants.h"
+#include "variants_linear.h"
 #include "variants_transpose.h"
 
 using namespace maxk;
@@ -107,8 +115,50 @@ static int check_transpose() {
   return finish();
 }
 
+// The tables of variants_linear.h: every D, and M up to past three wide panels; the panels cover M
+// without an empty one, the row groups stay within kLinGroups over all panels, and the scratch
+// sizes are the documented ones.
+static int check_linear() {
+  using namespace maxk_lin;
+  {
+    Family a("lin_matmul", kMatmulVariants);
+    Family b("lin_sampled", kSampledVariants);
+    Family c("lin_wgrad", kWeightGradVariants);
+    for (int d = 1; d <= 256; ++d)
+      for (int m = 1; m <= 400; ++m) {
+        a.selected(select_matmul_variant(d, m));
+        b.selected(select_sampled_variant(d, m));
+        c.selected(select_weight_grad_variant(d, m));
+        const int mp = panel_width(d, m);
+        const long long p = panel_count(d, m);
+        bool ok = (mp == 64 || mp == 128) && p * mp >= m && (p - 1) * mp < m &&
+                  4ll * (d * mp + d) <= 160 * 1024;
+        for (long long n : {0ll, 1ll, 16ll, 17ll, 4096ll, 4097ll, 232965ll, 2449029ll}) {
+          const long long w = row_groups(n, p);
+          ok = ok && w >= 1 && w * p <= (p > kLinGroups ? p : kLinGroups) &&
+               (w - 1) * kLinWaves < (n > 0 ? n : 1) &&
+               scratch_bytes(kLinMatmul, n, d, 1, m) == 0 &&
+               scratch_bytes(kLinSampled, n, d, d, m) == (p > 1 ? 4 * p * n * d : 0) &&
+               scratch_bytes(kLinWeightGrad, n, d, 1, m) == 4 * (p * w * d * mp + w * d);
+        }
+        if (!ok) {
+          std::fprintf(stderr, "linear: bad panel plan for D = %d, M = %d\n", d, m);
+          g_bad = 1;
+        }
+      }
+  }
+  if (scratch_bytes(3, 1, 8, 1, 1) != -1 || scratch_bytes(0, 1, 8, 9, 1) != -1 ||
+      scratch_bytes(0, 1, 257, 1, 1) != -1 || scratch_bytes(0, 1, 8, 1, 0) != -1 ||
+      scratch_bytes(0, -1, 8, 1, 1) != -1) {
+    std::fprintf(stderr, "linear: scratch_bytes accepts a shape outside the limits\n");
+    g_bad = 1;
+  }
+  return finish();
+}
+
 int main(int argc, char** argv) {
   if (argc > 1 && std::strcmp(argv[1], "transpose") == 0) return check_transpose();
+  if (argc > 1 && std::strcmp(argv[1], "linear") == 0) return check_linear();
   const bool tf[] = {false, true};
   {
     Family fam("forward", kFwdVariants);
