@@ -28,6 +28,7 @@ from .ops import (  # noqa: F401
     edge_softmax_row_limits,
     get_plan,
     heads_row_limits,
+    linear_topk,
     max_row_limits,
     maxk_backward,
     maxk_forward,
@@ -121,7 +122,7 @@ __all__ = [
     "node_subgraph", "Subgraph", "random_partition", "ClusterLoader", "subgraph_row_limits",
     "csr_transpose", "transpose_digit_bits",
     "cbsr_matmul", "cbsr_sampled_matmul", "cbsr_weight_grad", "cbsr_linear", "linear_maxk",
-    "CBSRMatmulFunction", "LinearMaxKFunction",
+    "CBSRMatmulFunction", "LinearMaxKFunction", "linear_topk",
 ]
 
 ABI_VERSION = lib.maxk_abi_version()

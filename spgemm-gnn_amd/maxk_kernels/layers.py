@@ -62,7 +62,9 @@ rows that are ``1 - k / D`` zeros. ``MaxKSAGEConv`` in its default ordering with
 ``sum`` aggregator computes ``x = feat_drop(MaxK(feat))`` as CBSR once, aggregates it with
 ``spgemm`` and takes the self term ``fc_self(x)`` from ``cbsr_linear``, so no dense masked row is
 built. ``MaxKGCNConv`` with its own ``weight`` takes ``MaxK(feat W)`` from ``linear_maxk``, whose
-backward never writes the ``[N, D]`` gradient of ``feat W`` and which needs ``topk_mode="exact"``.
+backward never writes the ``[N, D]`` gradient of ``feat W`` and which needs ``topk_mode="exact"``;
+with ``fused_linear=True`` as well (default off) its forward is the one launch of
+``ops.linear_topk``, which never writes ``feat W`` either.
 A sampled ``Block``, the other aggregators and orderings and ``nonlinear="relu"`` keep their
 present path. The options are off by default: measured, only the forward product is faster than
 the GEMM it replaces (README, "Measured results").
@@ -337,10 +339,11 @@ class MaxKGCNConv(nn.Module):
 
     def __init__(self, in_feats, out_feats, norm="both", weight=True, bias=True,
                  allow_zero_in_degree=False, maxk=32, topk_mode="exact", feat_drop=0.,
-                 nonlinear="maxk", fused_dropout=False, sparse_linear=False):
+                 nonlinear="maxk", fused_dropout=False, sparse_linear=False, fused_linear=False):
         super().__init__()
         self.fused_dropout = bool(fused_dropout)
         self.sparse_linear = bool(sparse_linear)
+        self.fused_linear = bool(fused_linear)  # with sparse_linear: linear_maxk(fused=True)
         if norm not in ("both", "right", "left", "none"):
             raise ValueError(f"Invalid norm value {norm!r}")
         self.in_feats = in_feats
@@ -369,7 +372,8 @@ class MaxKGCNConv(nn.Module):
             raise ValueError("Graph has nodes with zero in-degree")
         if self.sparse_linear and self.weight is not None and self.nonlinear == "maxk":
             # MaxK(feat W) whose backward takes the [N, k] gradient as it is
-            sp_data, sp_index = linear_maxk(feat, self.weight.t(), None, self.maxk, self.topk_mode)
+            sp_data, sp_index = linear_maxk(feat, self.weight.t(), None, self.maxk, self.topk_mode,
+                                            fused=self.fused_linear)
             sp_data = _sparse_dropout(sp_data, self.feat_drop, self.training)
             rst = spgemm(sp_data, sp_index, csr.with_values(self.norm), self.out_feats,
                          edge_weight=ew)

@@ -11,6 +11,8 @@ the masked rows are ``N D M`` on operands that are ``1 - k / D`` zeros. The thre
 * :func:`linear_maxk` is ``maxk(F.linear(h, weight, bias), k)`` whose backward takes the gradient
   of the kept values as it is: ``grad_h`` by (A) with ``weight`` as the table, ``grad_weight`` and
   ``grad_bias`` by (C) with ``h`` in the place of the gradient. No ``[N, D]`` gradient is written.
+  With ``fused=True`` the forward is ``ops.linear_topk``, one launch that keeps the ``[N, D]``
+  pre-activation in matrix-core accumulators, so that tensor is not written either.
 
 Both are first order only, as every Function of :mod:`maxk_kernels.autograd`.
 """
@@ -57,12 +59,18 @@ def cbsr_linear(sp_data: torch.Tensor, sp_index: torch.Tensor, weight: torch.Ten
 
 class LinearMaxKFunction(torch.autograd.Function):
     """``(h, weight [D, D_in], bias) -> maxk(h @ weight.T + bias, k)`` in exact mode; only ``h``
-    and the selectors are saved."""
+    and the selectors are saved. ``fused``: the forward is ``ops.linear_topk`` instead of
+    ``F.linear`` and ``ops.maxk_forward``; the backward is the same."""
 
     @staticmethod
-    def forward(ctx, h, weight, bias, k):
-        sp_data, sp_index = ops.maxk_forward(F.linear(h, weight, bias), k, mode="exact",
-                                             return_index=True)
+    def forward(ctx, h, weight, bias, k, fused=False):
+        if fused:
+            sp_data, sp_index = ops.linear_topk(
+                ops._rows_in_place(h), ops._rows_in_place(weight),
+                None if bias is None else bias.contiguous(), k)
+        else:
+            sp_data, sp_index = ops.maxk_forward(F.linear(h, weight, bias), k, mode="exact",
+                                                 return_index=True)
         ctx.save_for_backward(h, weight, sp_index)
         ctx.mark_non_differentiable(sp_index)
         return sp_data, sp_index
@@ -80,15 +88,18 @@ class LinearMaxKFunction(torch.autograd.Function):
             res = ops.cbsr_weight_grad(grad_data, sp_index, ops._rows_in_place(h),
                                        weight.shape[0], with_sum=bool(need[2]))
             grad_w, grad_b = res if need[2] else (res, None)
-        return grad_h, grad_w if need[1] else None, grad_b, None
+        return grad_h, grad_w if need[1] else None, grad_b, None, None
 
 
 def linear_maxk(h: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], k: int,
-                mode: str = "exact"):
+                mode: str = "exact", fused: bool = False):
     """``(sp_data, sp_index) = maxk(F.linear(h, weight, bias), k)`` for ``weight [D, D_in]``,
     differentiable in ``h``, ``weight`` and ``bias``. ``mode="ref_compat"`` is refused: its padding
-    slots carry no gradient, which takes the rule of the scatter (``autograd._mask_padding``)."""
+    slots carry no gradient, which takes the rule of the scatter (``autograd._mask_padding``).
+    ``fused=True`` computes the forward with ``ops.linear_topk`` (f32, ``D <= 256``): the same
+    selection rules on a pre-activation whose sum over ``D_in`` runs in the matrix cores' order, so
+    values agree with the default within rounding, and bit for bit on exactly summable inputs."""
     if mode != "exact":
         raise ValueError(f'linear_maxk supports mode="exact" only, got {mode!r}: the padding '
                          "slots of ref_compat need the MaxK scatter's rule")
-    return LinearMaxKFunction.apply(h, weight, bias, k)
+    return LinearMaxKFunction.apply(h, weight, bias, k, bool(fused))

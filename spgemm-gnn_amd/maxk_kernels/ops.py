@@ -1316,6 +1316,48 @@ def cbsr_weight_grad(sp_data, sp_index, g, dim_origin: int, with_sum: bool = Fal
 
 
 # -------------------------------------------------------------------------------------
+# Fused linear + MaxK (include/maxk_hip.h, "Fused linear + MaxK")
+# -------------------------------------------------------------------------------------
+def linear_topk_tile(dim_origin: int) -> Tuple[int, ...]:
+    """``(rows per work-group, accumulator columns, columns of dim_in per step, LDS bytes)`` of
+    the fused kernel for ``dim_origin`` (``maxk_linear_topk_tile``)."""
+    return _int32_list(lib.maxk_linear_topk_tile, int(dim_origin))
+
+
+def linear_topk(h, weight, bias, k: int, out=None, dense=None):
+    """``(sp_data, sp_index) = maxk(h @ weight.T + bias, k)`` in exact mode, one launch
+    (``maxk_linear_topk``): ``h`` f32 ``[N, D_in]``, ``weight`` f32 ``[D, D_in]``, ``bias`` f32
+    ``[D]`` or ``None``; the ``[N, D]`` pre-activation is never written. Rows of ``h``, ``weight``
+    and the outputs may be strided. ``out=(sp_data, sp_index)``: the ``[N, k]`` tables to write
+    into (f32, u8; the strided views of :meth:`GraphPlan.new_cbsr` are taken as they are).
+    ``dense``: an f32 ``[N, D]`` tensor that receives the dense masked row with the same launch
+    (the pre-activation at the selected features, ``+0.0`` elsewhere); it must not overlap ``h``."""
+    _need(isinstance(h, torch.Tensor) and h.is_cuda, "h must be a CUDA tensor")
+    dev = h.device
+    n, d_in, hs = _rows(h, "h", None, None, "num_rows, dim_in", dev)
+    d, _, ws = _rows(weight, "weight", None, d_in, "dim_origin, dim_in", dev)
+    _need(d_in >= 1, "h must have at least one column")
+    _need(d <= 256, "input dimension must be <= 256 (u8 selectors)")
+    k = int(k)
+    _need(1 <= k <= d, "k must be between 1 and input dimension")
+    if bias is not None:
+        _vector(bias, "bias", torch.float32, d, "dim_origin", dev)
+    if out is None:
+        out = (torch.empty((n, k), dtype=torch.float32, device=dev),
+               torch.empty((n, k), dtype=torch.uint8, device=dev))
+    sp_data, sp_index = out
+    _, _, ds, is_ = _heads_tables(sp_data, sp_index, dev)
+    _need(tuple(sp_data.shape) == (n, k) and tuple(sp_index.shape) == (n, k),
+          f"out must be two [{n}, {k}] tables")
+    dstride = _rows(dense, "dense", n, d, "num_rows, dim_origin", dev)[2] if dense is not None else 0
+    with _device(dev):
+        check(lib.maxk_linear_topk(_p(h), hs, _p(weight), ws, _p(bias), n, d_in, d, k, _p(sp_data),
+                                   ds, _p(sp_index), is_, _p(dense), dstride, _stream()),
+              "linear_topk")
+    return sp_data, sp_index
+
+
+# -------------------------------------------------------------------------------------
 # Max aggregation (include/maxk_hip.h, "Max aggregation")
 # -------------------------------------------------------------------------------------
 MAX_ROW_EDGES = 1 << 24  # the forward's precondition: every row is shorter than this

@@ -31,6 +31,11 @@ formula (the SSpMM backward) as a registered derivative.
                                   -> [N, D]   (MaxK that also emits the dense masked row; the
                                      scatter adds the dense row's gradient; p = 0: no dropout)
 
+    torch.ops.maxk.linear_topk(h, weight, bias (or None), k) -> (sp_data [N, k] f32, sp_index
+                                  [N, k] u8): maxk(h @ weight.T + bias, k) in one launch, the
+                                     [N, D] pre-activation never written; no derivative (use
+                                     maxk_kernels.linear_maxk(..., fused=True))
+
     torch.ops.maxk.csr_transpose(ptr, idx, val (or None), num_cols)
                                   -> (ptr_t [num_cols + 1], idx_t [E], order [E], val_t [E], all
                                      int32 but the f32 val_t, which is empty without val): A^T of a
@@ -303,6 +308,21 @@ def _maxk_dense_backward(ctx, grad_dense, grad_data, grad_index):
 
 
 maxk_dense_forward.register_autograd(_maxk_dense_backward, setup_context=_maxk_dense_setup)
+
+
+# maxk(h @ weight.T + bias, k) in one launch (ops.linear_topk). No derivative is registered:
+# maxk_kernels.linear_maxk(..., fused=True) is the differentiable form.
+@torch.library.custom_op(f"{_NS}::linear_topk", mutates_args=())
+def linear_topk(h: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
+                k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Fused linear + MaxK top-k -> CBSR, exact mode; the pre-activation is never written."""
+    return ops.linear_topk(h, weight, bias, k)
+
+
+@linear_topk.register_fake
+def _(h, weight, bias, k):
+    n = h.shape[0]
+    return (h.new_empty((n, k)), h.new_empty((n, k), dtype=torch.uint8))
 
 
 # A^T of a CSR graph (ops.csr_transpose). The output shapes follow from the input shapes and

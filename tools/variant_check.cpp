@@ -20,6 +20,12 @@
 // products over every D and the widths of M around the panel edges, with the panel cover and the
 // scratch sizes); their names are the panel kernels of
 // tests/golden/kernel_instantiations_linear.txt.
+//
+//   variant_check linear_topk
+//
+// does it for the table of csrc/variants_linear_topk.h (the fused linear + top-k kernel over every
+// D, with and without the dense row, and its LDS plan); its names are
+// tests/golden/kernel_instantiations_linear_topk.txt.
 #include <algorithm>
 #include <climits>
 #include <cstdio>
@@ -29,6 +35,7 @@
 
 #include "variants.h"
 #include "variants_linear.h"
+#include "variants_linear_topk.h"
 #include "variants_transpose.h"
 
 using namespace maxk;
@@ -156,9 +163,35 @@ static int check_linear() {
   return finish();
 }
 
+// The table of variants_linear_topk.h: every D with and without the dense row; the accumulators
+// cover D with the narrowest width, and the stage and the waves' epilogue rows fit the LDS twice.
+static int check_linear_topk() {
+  using namespace maxk_lt;
+  {
+    Family fam("linear_topk", kLinearTopkVariants);
+    for (int d = 1; d <= 256; ++d)
+      for (bool dense : {false, true}) {
+        const LinearTopkVariant v = select_linear_topk_variant(d, dense);
+        fam.selected(v);
+        const int dp = padded_dim(d);
+        const bool ok = v.dp == dp && v.dense == dense && dp >= d && (dp == 64 || dp / 2 < d) &&
+                        lds_bytes(dp) >= stage_bytes(dp) &&
+                        lds_bytes(dp) >= kLtWaves * wave_epilogue_bytes(dp) &&
+                        wave_epilogue_bytes(dp) % 16 == 0 && 2 * lds_bytes(dp) <= 160 * 1024 &&
+                        (kLtTileRows + dp) % 32 == 0;
+        if (!ok) {
+          std::fprintf(stderr, "linear_topk: bad tile plan for D = %d\n", d);
+          g_bad = 1;
+        }
+      }
+  }
+  return finish();
+}
+
 int main(int argc, char** argv) {
   if (argc > 1 && std::strcmp(argv[1], "transpose") == 0) return check_transpose();
   if (argc > 1 && std::strcmp(argv[1], "linear") == 0) return check_linear();
+  if (argc > 1 && std::strcmp(argv[1], "linear_topk") == 0) return check_linear_topk();
   const bool tf[] = {false, true};
   {
     Family fam("forward", kFwdVariants);
