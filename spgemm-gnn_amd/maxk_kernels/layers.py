@@ -64,7 +64,11 @@ rows that are ``1 - k / D`` zeros. ``MaxKSAGEConv`` in its default ordering with
 built. ``MaxKGCNConv`` with its own ``weight`` takes ``MaxK(feat W)`` from ``linear_maxk``, whose
 backward never writes the ``[N, D]`` gradient of ``feat W`` and which needs ``topk_mode="exact"``;
 with ``fused_linear=True`` as well (default off) its forward is the one launch of
-``ops.linear_topk``, which never writes ``feat W`` either.
+``ops.linear_topk``, which never writes ``feat W`` either; ``linear_dtype=torch.bfloat16`` or
+``torch.float16`` on top of both (default ``None``) casts ``feat`` and the weight to that type in
+front of it, so the product runs in the 16-bit kernel with f32 sums while the parameters, the
+tables and the gradients that reach the parameters stay f32. There are no autocast hooks: the
+option is explicit.
 A sampled ``Block``, the other aggregators and orderings and ``nonlinear="relu"`` keep their
 present path. The options are off by default: measured, only the forward product is faster than
 the GEMM it replaces (README, "Measured results").
@@ -339,11 +343,20 @@ class MaxKGCNConv(nn.Module):
 
     def __init__(self, in_feats, out_feats, norm="both", weight=True, bias=True,
                  allow_zero_in_degree=False, maxk=32, topk_mode="exact", feat_drop=0.,
-                 nonlinear="maxk", fused_dropout=False, sparse_linear=False, fused_linear=False):
+                 nonlinear="maxk", fused_dropout=False, sparse_linear=False, fused_linear=False,
+                 linear_dtype=None):
         super().__init__()
         self.fused_dropout = bool(fused_dropout)
         self.sparse_linear = bool(sparse_linear)
         self.fused_linear = bool(fused_linear)  # with sparse_linear: linear_maxk(fused=True)
+        if linear_dtype is not None:
+            if linear_dtype not in (torch.bfloat16, torch.float16):
+                raise ValueError(f"linear_dtype must be torch.bfloat16, torch.float16 or None, "
+                                 f"got {linear_dtype!r}")
+            if not (self.sparse_linear and self.fused_linear):
+                raise ValueError("linear_dtype needs sparse_linear=True and fused_linear=True: "
+                                 "only the fused linear + MaxK has a 16-bit kernel")
+        self.linear_dtype = linear_dtype  # operands of the fused product; parameters stay f32
         if norm not in ("both", "right", "left", "none"):
             raise ValueError(f"Invalid norm value {norm!r}")
         self.in_feats = in_feats
@@ -372,7 +385,10 @@ class MaxKGCNConv(nn.Module):
             raise ValueError("Graph has nodes with zero in-degree")
         if self.sparse_linear and self.weight is not None and self.nonlinear == "maxk":
             # MaxK(feat W) whose backward takes the [N, k] gradient as it is
-            sp_data, sp_index = linear_maxk(feat, self.weight.t(), None, self.maxk, self.topk_mode,
+            w_t = self.weight.t()
+            if self.linear_dtype is not None:  # differentiable casts: gradients arrive as f32
+                feat, w_t = feat.to(self.linear_dtype), w_t.to(self.linear_dtype)
+            sp_data, sp_index = linear_maxk(feat, w_t, None, self.maxk, self.topk_mode,
                                             fused=self.fused_linear)
             sp_data = _sparse_dropout(sp_data, self.feat_drop, self.training)
             rst = spgemm(sp_data, sp_index, csr.with_values(self.norm), self.out_feats,

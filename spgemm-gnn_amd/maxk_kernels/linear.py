@@ -12,7 +12,8 @@ the masked rows are ``N D M`` on operands that are ``1 - k / D`` zeros. The thre
   of the kept values as it is: ``grad_h`` by (A) with ``weight`` as the table, ``grad_weight`` and
   ``grad_bias`` by (C) with ``h`` in the place of the gradient. No ``[N, D]`` gradient is written.
   With ``fused=True`` the forward is ``ops.linear_topk``, one launch that keeps the ``[N, D]``
-  pre-activation in matrix-core accumulators, so that tensor is not written either.
+  pre-activation in matrix-core accumulators, so that tensor is not written either; with bf16 or
+  f16 ``h`` and ``weight`` it is the 16-bit kernel, and the backward upcasts.
 
 Both are first order only, as every Function of :mod:`maxk_kernels.autograd`.
 """
@@ -60,7 +61,9 @@ def cbsr_linear(sp_data: torch.Tensor, sp_index: torch.Tensor, weight: torch.Ten
 class LinearMaxKFunction(torch.autograd.Function):
     """``(h, weight [D, D_in], bias) -> maxk(h @ weight.T + bias, k)`` in exact mode; only ``h``
     and the selectors are saved. ``fused``: the forward is ``ops.linear_topk`` instead of
-    ``F.linear`` and ``ops.maxk_forward``; the backward is the same."""
+    ``F.linear`` and ``ops.maxk_forward``; the backward is the same. 16-bit ``h`` and ``weight``
+    (``fused`` only): ``sp_data`` is f32, the backward runs the f32 kernels on upcast copies of
+    ``weight`` and ``h`` and returns every gradient in its input's dtype."""
 
     @staticmethod
     def forward(ctx, h, weight, bias, k, fused=False):
@@ -72,6 +75,7 @@ class LinearMaxKFunction(torch.autograd.Function):
             sp_data, sp_index = ops.maxk_forward(F.linear(h, weight, bias), k, mode="exact",
                                                  return_index=True)
         ctx.save_for_backward(h, weight, sp_index)
+        ctx.bias_dtype = None if bias is None else bias.dtype
         ctx.mark_non_differentiable(sp_index)
         return sp_data, sp_index
 
@@ -83,11 +87,15 @@ class LinearMaxKFunction(torch.autograd.Function):
         need = ctx.needs_input_grad
         grad_h = grad_w = grad_b = None
         if need[0]:
-            grad_h = ops.cbsr_matmul(grad_data, sp_index, ops._rows_in_place(weight))
+            grad_h = ops.cbsr_matmul(grad_data, sp_index, ops._rows_in_place(weight.float()))
         if need[1] or need[2]:
-            res = ops.cbsr_weight_grad(grad_data, sp_index, ops._rows_in_place(h),
+            res = ops.cbsr_weight_grad(grad_data, sp_index, ops._rows_in_place(h.float()),
                                        weight.shape[0], with_sum=bool(need[2]))
             grad_w, grad_b = res if need[2] else (res, None)
+        if h.dtype != torch.float32:  # 16-bit inputs: one rounding of each f32 gradient
+            grad_h = None if grad_h is None else grad_h.to(h.dtype)
+            grad_w = None if grad_w is None else grad_w.to(weight.dtype)
+            grad_b = None if grad_b is None else grad_b.to(ctx.bias_dtype)
         return grad_h, grad_w if need[1] else None, grad_b, None, None
 
 
@@ -98,8 +106,17 @@ def linear_maxk(h: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tens
     slots carry no gradient, which takes the rule of the scatter (``autograd._mask_padding``).
     ``fused=True`` computes the forward with ``ops.linear_topk`` (f32, ``D <= 256``): the same
     selection rules on a pre-activation whose sum over ``D_in`` runs in the matrix cores' order, so
-    values agree with the default within rounding, and bit for bit on exactly summable inputs."""
+    values agree with the default within rounding, and bit for bit on exactly summable inputs.
+
+    The call follows the dtype of ``h`` and ``weight``. Both bf16 or both f16 needs ``fused=True``:
+    the forward is the 16-bit kernel of ``ops.linear_topk`` (f32 sums, ``sp_data`` f32). The
+    backward upcasts: it runs the f32 ``cbsr_matmul`` and ``cbsr_weight_grad`` on f32 copies of
+    ``weight`` and ``h`` and rounds ``grad_h`` and ``grad_weight`` to the inputs' dtype and
+    ``grad_bias`` to the bias's."""
     if mode != "exact":
         raise ValueError(f'linear_maxk supports mode="exact" only, got {mode!r}: the padding '
                          "slots of ref_compat need the MaxK scatter's rule")
+    if not fused and (h.dtype in ops.LINEAR_TOPK_DTYPES or weight.dtype in ops.LINEAR_TOPK_DTYPES):
+        raise ValueError(f"linear_maxk on {h.dtype} / {weight.dtype} inputs needs fused=True: only "
+                         "the fused forward has a 16-bit kernel")
     return LinearMaxKFunction.apply(h, weight, bias, k, bool(fused))

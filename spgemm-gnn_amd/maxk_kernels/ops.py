@@ -1235,14 +1235,14 @@ def cbsr_linear_panel(dim_origin: int, dim_m: int) -> Tuple[int, ...]:
     return _int32_list(lib.maxk_cbsr_linear_panel, int(dim_origin), int(dim_m))
 
 
-def _rows(t, name: str, rows, cols, shape_name: str, dev):
-    """An f32 ``[rows, cols]`` tensor (``None``: any extent) on ``dev`` whose rows may be strided:
-    ``(rows, cols, row stride)``."""
+def _rows(t, name: str, rows, cols, shape_name: str, dev, dtype=torch.float32):
+    """A ``dtype`` (f32) ``[rows, cols]`` tensor (``None``: any extent) on ``dev`` whose rows may
+    be strided: ``(rows, cols, row stride)``."""
     _need(isinstance(t, torch.Tensor) and t.dim() == 2 and
           (rows is None or t.shape[0] == rows) and (cols is None or t.shape[1] == cols),
           f"{name} must be [{shape_name}]")
     _need(t.device == dev, "all tensors must be on the same device")
-    return t.shape[0], t.shape[1], _table(t, name, torch.float32, t.shape[0], t.shape[1])
+    return t.shape[0], t.shape[1], _table(t, name, dtype, t.shape[0], t.shape[1])
 
 
 def cbsr_matmul(sp_data, sp_index, table, bias=None, out=None) -> torch.Tensor:
@@ -1318,29 +1318,49 @@ def cbsr_weight_grad(sp_data, sp_index, g, dim_origin: int, with_sum: bool = Fal
 # -------------------------------------------------------------------------------------
 # Fused linear + MaxK (include/maxk_hip.h, "Fused linear + MaxK")
 # -------------------------------------------------------------------------------------
-def linear_topk_tile(dim_origin: int) -> Tuple[int, ...]:
+# dtype argument of maxk_linear_topk_16 (MAXK_DTYPE_BF16, MAXK_DTYPE_F16)
+LINEAR_TOPK_DTYPES = {torch.bfloat16: 1, torch.float16: 2}
+
+
+def linear_topk_tile(dim_origin: int, dtype: torch.dtype = torch.float32) -> Tuple[int, ...]:
     """``(rows per work-group, accumulator columns, columns of dim_in per step, LDS bytes)`` of
-    the fused kernel for ``dim_origin`` (``maxk_linear_topk_tile``)."""
-    return _int32_list(lib.maxk_linear_topk_tile, int(dim_origin))
+    the fused kernel for ``dim_origin`` and operands of ``dtype``: ``maxk_linear_topk_tile`` for
+    f32, ``maxk_linear_topk_16_tile`` for bf16 and f16."""
+    _need(dtype == torch.float32 or dtype in LINEAR_TOPK_DTYPES,
+          "dtype must be float32, bfloat16 or float16")
+    fn = lib.maxk_linear_topk_tile if dtype == torch.float32 else lib.maxk_linear_topk_16_tile
+    return _int32_list(fn, int(dim_origin))
 
 
 def linear_topk(h, weight, bias, k: int, out=None, dense=None):
-    """``(sp_data, sp_index) = maxk(h @ weight.T + bias, k)`` in exact mode, one launch
-    (``maxk_linear_topk``): ``h`` f32 ``[N, D_in]``, ``weight`` f32 ``[D, D_in]``, ``bias`` f32
-    ``[D]`` or ``None``; the ``[N, D]`` pre-activation is never written. Rows of ``h``, ``weight``
-    and the outputs may be strided. ``out=(sp_data, sp_index)``: the ``[N, k]`` tables to write
-    into (f32, u8; the strided views of :meth:`GraphPlan.new_cbsr` are taken as they are).
-    ``dense``: an f32 ``[N, D]`` tensor that receives the dense masked row with the same launch
-    (the pre-activation at the selected features, ``+0.0`` elsewhere); it must not overlap ``h``."""
-    _need(isinstance(h, torch.Tensor) and h.is_cuda, "h must be a CUDA tensor")
+    """``(sp_data, sp_index) = maxk(h @ weight.T + bias, k)`` in exact mode, one launch:
+    ``h`` ``[N, D_in]`` and ``weight`` ``[D, D_in]`` of one dtype out of f32 (``maxk_linear_topk``),
+    bf16 and f16 (``maxk_linear_topk_16``: 16-bit operands, f32 sums), ``bias`` ``[D]`` or
+    ``None``, f32 or, with 16-bit operands, their dtype (upcast here, which is exact); the
+    ``[N, D]`` pre-activation is never written and the outputs are f32 / u8 whatever the inputs.
+    Rows of ``h``, ``weight`` and the outputs may be strided. ``out=(sp_data, sp_index)``: the
+    ``[N, k]`` tables to write into (f32, u8; the strided views of :meth:`GraphPlan.new_cbsr` are
+    taken as they are). ``dense``: an f32 ``[N, D]`` tensor that receives the dense masked row with
+    the same launch (the pre-activation at the selected features, ``+0.0`` elsewhere); it must not
+    overlap ``h``."""
+    _need(isinstance(h, torch.Tensor) and isinstance(weight, torch.Tensor),
+          "h and weight must be tensors")
+    _need(weight.dtype == h.dtype, f"h and weight must have one dtype, got {h.dtype} and "
+                                   f"{weight.dtype}: cast one of them")
+    code = LINEAR_TOPK_DTYPES.get(h.dtype)
+    _need(code is not None or h.dtype == torch.float32,
+          "h and weight must be float32, bfloat16 or float16")
+    _need(h.is_cuda, "h must be a CUDA tensor")
     dev = h.device
-    n, d_in, hs = _rows(h, "h", None, None, "num_rows, dim_in", dev)
-    d, _, ws = _rows(weight, "weight", None, d_in, "dim_origin, dim_in", dev)
+    n, d_in, hs = _rows(h, "h", None, None, "num_rows, dim_in", dev, h.dtype)
+    d, _, ws = _rows(weight, "weight", None, d_in, "dim_origin, dim_in", dev, h.dtype)
     _need(d_in >= 1, "h must have at least one column")
     _need(d <= 256, "input dimension must be <= 256 (u8 selectors)")
     k = int(k)
     _need(1 <= k <= d, "k must be between 1 and input dimension")
     if bias is not None:
+        if code is not None and isinstance(bias, torch.Tensor) and bias.dtype == h.dtype:
+            bias = bias.float()
         _vector(bias, "bias", torch.float32, d, "dim_origin", dev)
     if out is None:
         out = (torch.empty((n, k), dtype=torch.float32, device=dev),
@@ -1350,6 +1370,13 @@ def linear_topk(h, weight, bias, k: int, out=None, dense=None):
     _need(tuple(sp_data.shape) == (n, k) and tuple(sp_index.shape) == (n, k),
           f"out must be two [{n}, {k}] tables")
     dstride = _rows(dense, "dense", n, d, "num_rows, dim_origin", dev)[2] if dense is not None else 0
+    if code is not None:
+        with _device(dev):
+            check(lib.maxk_linear_topk_16(_p(h), hs, _p(weight), ws, _p(bias), code, n, d_in, d, k,
+                                          _p(sp_data), ds, _p(sp_index), is_, _p(dense), dstride,
+                                          _stream()),
+                  "linear_topk")
+        return sp_data, sp_index
     with _device(dev):
         check(lib.maxk_linear_topk(_p(h), hs, _p(weight), ws, _p(bias), n, d_in, d, k, _p(sp_data),
                                    ds, _p(sp_index), is_, _p(dense), dstride, _stream()),

@@ -33,7 +33,8 @@ formula (the SSpMM backward) as a registered derivative.
 
     torch.ops.maxk.linear_topk(h, weight, bias (or None), k) -> (sp_data [N, k] f32, sp_index
                                   [N, k] u8): maxk(h @ weight.T + bias, k) in one launch, the
-                                     [N, D] pre-activation never written; no derivative (use
+                                     [N, D] pre-activation never written; h and weight of one
+                                     dtype out of f32, bf16, f16; no derivative (use
                                      maxk_kernels.linear_maxk(..., fused=True))
 
     torch.ops.maxk.csr_transpose(ptr, idx, val (or None), num_cols)
@@ -322,7 +323,7 @@ def linear_topk(h: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tens
 @linear_topk.register_fake
 def _(h, weight, bias, k):
     n = h.shape[0]
-    return (h.new_empty((n, k)), h.new_empty((n, k), dtype=torch.uint8))
+    return (h.new_empty((n, k), dtype=torch.float32), h.new_empty((n, k), dtype=torch.uint8))
 
 
 # A^T of a CSR graph (ops.csr_transpose). The output shapes follow from the input shapes and

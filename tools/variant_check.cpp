@@ -26,6 +26,12 @@
 // does it for the table of csrc/variants_linear_topk.h (the fused linear + top-k kernel over every
 // D, with and without the dense row, and its LDS plan); its names are
 // tests/golden/kernel_instantiations_linear_topk.txt.
+//
+//   variant_check linear_topk16
+//
+// does it for the table of csrc/variants_linear_topk16.h (the 16-bit fused kernel over every D,
+// with and without the dense row, for bf16 and f16, and its LDS plan); its names are
+// tests/golden/kernel_instantiations_linear_topk16.txt.
 #include <algorithm>
 #include <climits>
 #include <cstdio>
@@ -36,6 +42,7 @@
 #include "variants.h"
 #include "variants_linear.h"
 #include "variants_linear_topk.h"
+#include "variants_linear_topk16.h"
 #include "variants_transpose.h"
 
 using namespace maxk;
@@ -188,10 +195,40 @@ static int check_linear_topk() {
   return finish();
 }
 
+// The table of variants_linear_topk16.h: every D with and without the dense row in both types; the
+// accumulators cover D with the narrowest width, the rounds of 16-byte loads cover the stage's rows
+// and a staged row is whole MFMA steps, and the stage and the waves' epilogue rows fit the LDS
+// twice.
+static int check_linear_topk16() {
+  using namespace maxk_lt16;
+  {
+    Family fam("linear_topk16", kLinearTopk16Variants);
+    for (int d = 1; d <= 256; ++d)
+      for (bool dense : {false, true})
+        for (int dt : {kBf16, kF16}) {
+          const LinearTopk16Variant v = select_linear_topk16_variant(d, dense, dt);
+          fam.selected(v);
+          const int dp = padded_dim(d);
+          const bool ok = v.dp == dp && v.dense == dense && v.dtype == dt && dp >= d &&
+                          (dp == 64 || dp / 2 < d) && lds_bytes(dp) >= stage_bytes(dp) &&
+                          lds_bytes(dp) >= kWaves * wave_epilogue_bytes(dp) &&
+                          wave_epilogue_bytes(dp) % 16 == 0 && 2 * lds_bytes(dp) <= 160 * 1024 &&
+                          (kTileRows + dp) % kLoadRows == 0 && kChunk % kStep == 0 &&
+                          (2 * kRowElems) % 16 == 0;
+          if (!ok) {
+            std::fprintf(stderr, "linear_topk16: bad tile plan for D = %d\n", d);
+            g_bad = 1;
+          }
+        }
+  }
+  return finish();
+}
+
 int main(int argc, char** argv) {
   if (argc > 1 && std::strcmp(argv[1], "transpose") == 0) return check_transpose();
   if (argc > 1 && std::strcmp(argv[1], "linear") == 0) return check_linear();
   if (argc > 1 && std::strcmp(argv[1], "linear_topk") == 0) return check_linear_topk();
+  if (argc > 1 && std::strcmp(argv[1], "linear_topk16") == 0) return check_linear_topk16();
   const bool tf[] = {false, true};
   {
     Family fam("forward", kFwdVariants);
