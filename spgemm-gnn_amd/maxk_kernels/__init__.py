@@ -21,6 +21,7 @@ from .ops import (  # noqa: F401
     cbsr_sampled_matmul,
     cbsr_stats,
     cbsr_weight_grad,
+    cbsr_weight_grad_16,
     csr_transpose,
     clear_plan_cache,
     dense_spmm,
@@ -122,7 +123,7 @@ __all__ = [
     "node_subgraph", "Subgraph", "random_partition", "ClusterLoader", "subgraph_row_limits",
     "csr_transpose", "transpose_digit_bits",
     "cbsr_matmul", "cbsr_sampled_matmul", "cbsr_weight_grad", "cbsr_linear", "linear_maxk",
-    "CBSRMatmulFunction", "LinearMaxKFunction", "linear_topk",
+    "CBSRMatmulFunction", "LinearMaxKFunction", "linear_topk", "cbsr_weight_grad_16",
 ]
 
 ABI_VERSION = lib.maxk_abi_version()

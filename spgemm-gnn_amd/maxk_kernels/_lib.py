@@ -155,6 +155,10 @@ SIGNATURES = {
     "maxk_linear_topk_16": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32,
                                            _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "maxk_linear_topk_16_tile": (ctypes.c_int, [_i32, _vp, _i32]),
+    "maxk_cbsr_weight_grad_16": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i64,
+                                                _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
+    "maxk_cbsr_weight_grad_16_scratch_bytes": (ctypes.c_int64, [_i32, _i32, _i32, _i32]),
+    "maxk_cbsr_weight_grad_16_tile": (ctypes.c_int, [_i32, _i32, _vp, _i32]),
     "maxk_dense_spmm_csr": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "maxk_warp4_build": (ctypes.c_int, [_vp, _i32, _i32, _vp, _i64, ctypes.POINTER(_i64)]),
 }

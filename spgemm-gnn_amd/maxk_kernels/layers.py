@@ -67,8 +67,10 @@ with ``fused_linear=True`` as well (default off) its forward is the one launch o
 ``ops.linear_topk``, which never writes ``feat W`` either; ``linear_dtype=torch.bfloat16`` or
 ``torch.float16`` on top of both (default ``None``) casts ``feat`` and the weight to that type in
 front of it, so the product runs in the 16-bit kernel with f32 sums while the parameters, the
-tables and the gradients that reach the parameters stay f32. There are no autocast hooks: the
-option is explicit.
+tables and the gradients that reach the parameters stay f32; ``weight_grad_16=True`` on top of
+``linear_dtype`` (default off) computes the weight gradient of that product on the matrix cores
+from the 16-bit ``feat`` as it is (``ops.cbsr_weight_grad_16``), without an f32 copy of it. There
+are no autocast hooks: the options are explicit.
 A sampled ``Block``, the other aggregators and orderings and ``nonlinear="relu"`` keep their
 present path. The options are off by default: measured, only the forward product is faster than
 the GEMM it replaces (README, "Measured results").
@@ -344,7 +346,7 @@ class MaxKGCNConv(nn.Module):
     def __init__(self, in_feats, out_feats, norm="both", weight=True, bias=True,
                  allow_zero_in_degree=False, maxk=32, topk_mode="exact", feat_drop=0.,
                  nonlinear="maxk", fused_dropout=False, sparse_linear=False, fused_linear=False,
-                 linear_dtype=None):
+                 linear_dtype=None, weight_grad_16=False):
         super().__init__()
         self.fused_dropout = bool(fused_dropout)
         self.sparse_linear = bool(sparse_linear)
@@ -357,6 +359,10 @@ class MaxKGCNConv(nn.Module):
                 raise ValueError("linear_dtype needs sparse_linear=True and fused_linear=True: "
                                  "only the fused linear + MaxK has a 16-bit kernel")
         self.linear_dtype = linear_dtype  # operands of the fused product; parameters stay f32
+        if weight_grad_16 and linear_dtype is None:
+            raise ValueError("weight_grad_16 needs linear_dtype: the 16-bit weight gradient reads "
+                             "the 16-bit operand of the fused linear + MaxK")
+        self.weight_grad_16 = bool(weight_grad_16)
         if norm not in ("both", "right", "left", "none"):
             raise ValueError(f"Invalid norm value {norm!r}")
         self.in_feats = in_feats
@@ -389,7 +395,8 @@ class MaxKGCNConv(nn.Module):
             if self.linear_dtype is not None:  # differentiable casts: gradients arrive as f32
                 feat, w_t = feat.to(self.linear_dtype), w_t.to(self.linear_dtype)
             sp_data, sp_index = linear_maxk(feat, w_t, None, self.maxk, self.topk_mode,
-                                            fused=self.fused_linear)
+                                            fused=self.fused_linear,
+                                            weight_grad_16=self.weight_grad_16)
             sp_data = _sparse_dropout(sp_data, self.feat_drop, self.training)
             rst = spgemm(sp_data, sp_index, csr.with_values(self.norm), self.out_feats,
                          edge_weight=ew)

@@ -1384,6 +1384,51 @@ def linear_topk(h, weight, bias, k: int, out=None, dense=None):
     return sp_data, sp_index
 
 
+def cbsr_weight_grad_16_scratch_bytes(num_rows: int, dim_origin: int, dim_k: int,
+                                      dim_m: int) -> int:
+    return int(lib.maxk_cbsr_weight_grad_16_scratch_bytes(int(num_rows), int(dim_origin),
+                                                          int(dim_k), int(dim_m)))
+
+
+def cbsr_weight_grad_16_tile(dim_origin: int, dim_m: int) -> Tuple[int, ...]:
+    """``(accumulator feature rows, panel width, panels, rows per chunk, most work-groups along the
+    rows of a panel, LDS bytes)`` of ``maxk_cbsr_weight_grad_16`` for a ``[dim_origin, dim_m]``
+    gradient (``maxk_cbsr_weight_grad_16_tile``)."""
+    return _int32_list(lib.maxk_cbsr_weight_grad_16_tile, int(dim_origin), int(dim_m))
+
+
+def cbsr_weight_grad_16(sp_data, sp_index, g, dim_origin: int, with_sum: bool = False, out=None,
+                        scratch=None):
+    """``densify(sp_data.to(g.dtype), sp_index).T @ g`` on the matrix cores: f32 ``[D, M]`` from
+    the CBSR tables ``[N, k]`` (f32 values, rounded to the type of ``g`` before the product) and
+    ``g`` bf16 or f16 ``[N, M]``; with ``with_sum`` also the column sums of the rounded
+    ``densify``, f32 ``[D]``, as ``(grad_table, grad_sum)`` (``maxk_cbsr_weight_grad_16``: f32
+    sums of exact products in a fixed order, distinct selectors within a row). ``out``: the
+    tensor(s) to write into; ``scratch``: a u8 tensor of at least
+    :func:`cbsr_weight_grad_16_scratch_bytes` bytes."""
+    code = LINEAR_TOPK_DTYPES.get(g.dtype) if isinstance(g, torch.Tensor) else None
+    _need(code is not None, "g must be bfloat16 or float16")
+    dev = sp_data.device if isinstance(sp_data, torch.Tensor) else None
+    n, k, ds, is_ = _heads_tables(sp_data, sp_index, dev)
+    d = int(dim_origin)
+    _need(1 <= k <= d <= 256, "k must be between 1 and input dimension")
+    m, gs = _rows(g, "g", n, None, "num_rows, dim_m", dev, g.dtype)[1:]
+    _need(m >= 1, "g must have at least one column")
+    grad_table, grad_sum = (out if with_sum else (out, None)) if out is not None else (None, None)
+    if grad_table is None:
+        grad_table = torch.empty((d, m), dtype=torch.float32, device=dev)
+    dts = _rows(grad_table, "out", d, m, "dim_origin, dim_m", dev)[2]
+    if with_sum:
+        grad_sum = _out_vector(grad_sum, "out[1]", d, "dim_origin", dev)
+    scratch = _scratch(scratch, cbsr_weight_grad_16_scratch_bytes(n, d, k, m), dev)
+    with _device(dev):
+        check(lib.maxk_cbsr_weight_grad_16(_p(sp_data), ds, _p(sp_index), is_, _p(g), gs, code,
+                                           _p(grad_table), dts, _p(grad_sum), _p(scratch),
+                                           scratch.numel(), n, d, k, m, _stream()),
+              "cbsr_weight_grad_16")
+    return (grad_table, grad_sum) if with_sum else grad_table
+
+
 # -------------------------------------------------------------------------------------
 # Max aggregation (include/maxk_hip.h, "Max aggregation")
 # -------------------------------------------------------------------------------------

@@ -37,6 +37,11 @@ formula (the SSpMM backward) as a registered derivative.
                                      dtype out of f32, bf16, f16; no derivative (use
                                      maxk_kernels.linear_maxk(..., fused=True))
 
+    torch.ops.maxk.cbsr_weight_grad_16(sp_data, sp_index, g, dim_origin) -> (grad_table
+                                  [dim_origin, M] f32, grad_sum [dim_origin] f32):
+                                     densify(sp_data.to(g.dtype), sp_index).T @ g and its column
+                                     sums for a bf16 / f16 g, on the matrix cores; no derivative
+
     torch.ops.maxk.csr_transpose(ptr, idx, val (or None), num_cols)
                                   -> (ptr_t [num_cols + 1], idx_t [E], order [E], val_t [E], all
                                      int32 but the f32 val_t, which is empty without val): A^T of a
@@ -324,6 +329,21 @@ def linear_topk(h: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tens
 def _(h, weight, bias, k):
     n = h.shape[0]
     return (h.new_empty((n, k), dtype=torch.float32), h.new_empty((n, k), dtype=torch.uint8))
+
+
+# The 16-bit weight and bias gradient of linear_maxk(..., fused=True, weight_grad_16=True)
+# (ops.cbsr_weight_grad_16). It is itself a backward: no derivative is registered.
+@torch.library.custom_op(f"{_NS}::cbsr_weight_grad_16", mutates_args=())
+def cbsr_weight_grad_16(sp_data: torch.Tensor, sp_index: torch.Tensor, g: torch.Tensor,
+                        dim_origin: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(grad_table [dim_origin, M], grad_sum [dim_origin])``, both f32."""
+    return ops.cbsr_weight_grad_16(sp_data, sp_index, g, dim_origin, with_sum=True)
+
+
+@cbsr_weight_grad_16.register_fake
+def _(sp_data, sp_index, g, dim_origin):
+    return (g.new_empty((dim_origin, g.shape[1]), dtype=torch.float32),
+            g.new_empty((dim_origin,), dtype=torch.float32))
 
 
 # A^T of a CSR graph (ops.csr_transpose). The output shapes follow from the input shapes and

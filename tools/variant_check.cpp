@@ -32,6 +32,13 @@
 // does it for the table of csrc/variants_linear_topk16.h (the 16-bit fused kernel over every D,
 // with and without the dense row, for bf16 and f16, and its LDS plan); its names are
 // tests/golden/kernel_instantiations_linear_topk16.txt.
+//
+//   variant_check weight_grad16
+//
+// does it for the table of csrc/variants_weight_grad16.h (the 16-bit weight gradient over every D,
+// the widths of M around the panel edges and both types, with its wave tiling, LDS plan, row
+// groups, scratch sizes and depth positions); its names are
+// tests/golden/kernel_instantiations_weight_grad16.txt.
 #include <algorithm>
 #include <climits>
 #include <cstdio>
@@ -44,6 +51,7 @@
 #include "variants_linear_topk.h"
 #include "variants_linear_topk16.h"
 #include "variants_transpose.h"
+#include "variants_weight_grad16.h"
 
 using namespace maxk;
 
@@ -224,11 +232,66 @@ static int check_linear_topk16() {
   return finish();
 }
 
+// The table of variants_weight_grad16.h: every D, M up to past three wide panels and both types; the
+// panels cover M without an empty one, the 8 waves tile the [DP, MP] accumulator in whole 16 x 16
+// tiles, two work-groups fit the LDS, the row groups stay within kGroups over all panels with no
+// group left without a chunk, the scratch is the documented one, and the depth positions of a step
+// are a permutation whose two halves are what one transposing read and one 16-byte read deliver.
+static int check_weight_grad16() {
+  using namespace maxk_wg16;
+  {
+    Family fam("weight_grad16", kWeightGrad16Variants);
+    for (int d = 1; d <= 256; ++d)
+      for (int m = 1; m <= 400; ++m)
+        for (int dt : {kBf16, kF16}) {
+          const WeightGrad16Variant v = select_weight_grad16_variant(d, m, dt);
+          fam.selected(v);
+          const int dp = padded_dim(d), mp = panel_width(m);
+          const long long p = panel_count(m);
+          const int wf = waves_along_features(dp), wc = kWaves / wf;
+          bool ok = v.dp == dp && v.mp == mp && v.dtype == dt && dp >= d &&
+                    (dp == 64 || dp / 2 < d) && (mp == 64 || mp == 128) && p * mp >= m &&
+                    (p - 1) * mp < m && wf * wc == kWaves && (dp / 16) % wf == 0 &&
+                    (mp / 16) % wc == 0 && 2 * lds_bytes(dp, mp) <= 160 * 1024 &&
+                    (2 * (mp + kGPad)) % 16 == 0 && (2 * kARow) % 16 == 0 &&
+                    kThreads % (mp / 8) == 0 && kChunkRows % (kThreads / (mp / 8)) == 0;
+          for (long long n : {0ll, 1ll, 64ll, 65ll, 8192ll, 8193ll, 232965ll, 2449029ll}) {
+            const long long w = row_groups(n, p), chunks = (n + kChunkRows - 1) / kChunkRows;
+            ok = ok && w >= 1 && w * p <= (p > kGroups ? p : kGroups) &&
+                 w <= (chunks > 0 ? chunks : 1) && w <= group_cap(p) &&
+                 scratch_bytes(n, d, 1, m) == 4 * (p * w * d * mp + w * d);
+          }
+          if (!ok) {
+            std::fprintf(stderr, "weight_grad16: bad tile plan for D = %d, M = %d\n", d, m);
+            g_bad = 1;
+          }
+        }
+  }
+  unsigned seen = 0;
+  for (int r = 0; r < kStep; ++r) {
+    const int pos = depth_position(r), q = pos / 8, e = pos % 8;
+    seen |= 1u << pos;
+    // lane (i, q) holds positions 8 q + e: rows 4 q + e of the first read, 16 + 4 q + e - 4 of the second
+    if (r != (e < 4 ? 4 * q + e : 16 + 4 * q + e - 4)) {
+      std::fprintf(stderr, "weight_grad16: row %d sits at depth position %d\n", r, pos);
+      g_bad = 1;
+    }
+  }
+  if (seen != 0xffffffffu || scratch_bytes(1, 8, 9, 1) != -1 || scratch_bytes(1, 257, 1, 1) != -1 ||
+      scratch_bytes(1, 8, 1, 0) != -1 || scratch_bytes(-1, 8, 1, 1) != -1 ||
+      scratch_bytes(1, 8, 0, 1) != -1) {
+    std::fprintf(stderr, "weight_grad16: depth positions or scratch limits are off\n");
+    g_bad = 1;
+  }
+  return finish();
+}
+
 int main(int argc, char** argv) {
   if (argc > 1 && std::strcmp(argv[1], "transpose") == 0) return check_transpose();
   if (argc > 1 && std::strcmp(argv[1], "linear") == 0) return check_linear();
   if (argc > 1 && std::strcmp(argv[1], "linear_topk") == 0) return check_linear_topk();
   if (argc > 1 && std::strcmp(argv[1], "linear_topk16") == 0) return check_linear_topk16();
+  if (argc > 1 && std::strcmp(argv[1], "weight_grad16") == 0) return check_weight_grad16();
   const bool tf[] = {false, true};
   {
     Family fam("forward", kFwdVariants);
