@@ -22,6 +22,7 @@ from .ops import (  # noqa: F401
     cbsr_stats,
     cbsr_weight_grad,
     cbsr_weight_grad_16,
+    cbsr_matmul_16,
     csr_transpose,
     clear_plan_cache,
     dense_spmm,
@@ -124,6 +125,7 @@ __all__ = [
     "csr_transpose", "transpose_digit_bits",
     "cbsr_matmul", "cbsr_sampled_matmul", "cbsr_weight_grad", "cbsr_linear", "linear_maxk",
     "CBSRMatmulFunction", "LinearMaxKFunction", "linear_topk", "cbsr_weight_grad_16",
+    "cbsr_matmul_16",
 ]
 
 ABI_VERSION = lib.maxk_abi_version()

@@ -159,6 +159,9 @@ SIGNATURES = {
                                                 _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "maxk_cbsr_weight_grad_16_scratch_bytes": (ctypes.c_int64, [_i32, _i32, _i32, _i32]),
     "maxk_cbsr_weight_grad_16_tile": (ctypes.c_int, [_i32, _i32, _vp, _i32]),
+    "maxk_cbsr_matmul_16": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _i32,
+                                           _i32, _i32, _i32, _i32, _vp]),
+    "maxk_cbsr_matmul_16_tile": (ctypes.c_int, [_i32, _i32, _vp, _i32]),
     "maxk_dense_spmm_csr": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "maxk_warp4_build": (ctypes.c_int, [_vp, _i32, _i32, _vp, _i64, ctypes.POINTER(_i64)]),
 }

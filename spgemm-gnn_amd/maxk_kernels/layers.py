@@ -69,8 +69,9 @@ with ``fused_linear=True`` as well (default off) its forward is the one launch o
 front of it, so the product runs in the 16-bit kernel with f32 sums while the parameters, the
 tables and the gradients that reach the parameters stay f32; ``weight_grad_16=True`` on top of
 ``linear_dtype`` (default off) computes the weight gradient of that product on the matrix cores
-from the 16-bit ``feat`` as it is (``ops.cbsr_weight_grad_16``), without an f32 copy of it. There
-are no autocast hooks: the options are explicit.
+from the 16-bit ``feat`` as it is (``ops.cbsr_weight_grad_16``), without an f32 copy of it, and
+``input_grad_16=True`` (the same) the gradient of ``feat`` from the 16-bit weight as it is
+(``ops.cbsr_matmul_16``). There are no autocast hooks: the options are explicit.
 A sampled ``Block``, the other aggregators and orderings and ``nonlinear="relu"`` keep their
 present path. The options are off by default: measured, only the forward product is faster than
 the GEMM it replaces (README, "Measured results").
@@ -346,7 +347,7 @@ class MaxKGCNConv(nn.Module):
     def __init__(self, in_feats, out_feats, norm="both", weight=True, bias=True,
                  allow_zero_in_degree=False, maxk=32, topk_mode="exact", feat_drop=0.,
                  nonlinear="maxk", fused_dropout=False, sparse_linear=False, fused_linear=False,
-                 linear_dtype=None, weight_grad_16=False):
+                 linear_dtype=None, weight_grad_16=False, input_grad_16=False):
         super().__init__()
         self.fused_dropout = bool(fused_dropout)
         self.sparse_linear = bool(sparse_linear)
@@ -363,6 +364,10 @@ class MaxKGCNConv(nn.Module):
             raise ValueError("weight_grad_16 needs linear_dtype: the 16-bit weight gradient reads "
                              "the 16-bit operand of the fused linear + MaxK")
         self.weight_grad_16 = bool(weight_grad_16)
+        if input_grad_16 and linear_dtype is None:
+            raise ValueError("input_grad_16 needs linear_dtype: the 16-bit input gradient reads the "
+                             "16-bit weight of the fused linear + MaxK")
+        self.input_grad_16 = bool(input_grad_16)
         if norm not in ("both", "right", "left", "none"):
             raise ValueError(f"Invalid norm value {norm!r}")
         self.in_feats = in_feats
@@ -396,7 +401,8 @@ class MaxKGCNConv(nn.Module):
                 feat, w_t = feat.to(self.linear_dtype), w_t.to(self.linear_dtype)
             sp_data, sp_index = linear_maxk(feat, w_t, None, self.maxk, self.topk_mode,
                                             fused=self.fused_linear,
-                                            weight_grad_16=self.weight_grad_16)
+                                            weight_grad_16=self.weight_grad_16,
+                                            input_grad_16=self.input_grad_16)
             sp_data = _sparse_dropout(sp_data, self.feat_drop, self.training)
             rst = spgemm(sp_data, sp_index, csr.with_values(self.norm), self.out_feats,
                          edge_weight=ew)

@@ -15,7 +15,8 @@ the masked rows are ``N D M`` on operands that are ``1 - k / D`` zeros. The thre
   pre-activation in matrix-core accumulators, so that tensor is not written either; with bf16 or
   f16 ``h`` and ``weight`` it is the 16-bit kernel, and the backward upcasts, unless
   ``weight_grad_16=True`` hands the weight and bias gradient to ``ops.cbsr_weight_grad_16``, which
-  reads the 16-bit ``h`` as it is on the matrix cores.
+  reads the 16-bit ``h`` as it is on the matrix cores, and ``input_grad_16=True`` the input
+  gradient to ``ops.cbsr_matmul_16``, which reads the 16-bit ``weight`` as it is there.
 
 Both are first order only, as every Function of :mod:`maxk_kernels.autograd`.
 """
@@ -66,10 +67,11 @@ class LinearMaxKFunction(torch.autograd.Function):
     ``F.linear`` and ``ops.maxk_forward``; the backward is the same. 16-bit ``h`` and ``weight``
     (``fused`` only): ``sp_data`` is f32, the backward runs the f32 kernels on upcast copies of
     ``weight`` and ``h`` and returns every gradient in its input's dtype; ``weight_grad_16``: the
-    weight and bias gradient come from ``ops.cbsr_weight_grad_16`` on ``h`` as it is."""
+    weight and bias gradient come from ``ops.cbsr_weight_grad_16`` on ``h`` as it is;
+    ``input_grad_16``: ``grad_h`` comes from ``ops.cbsr_matmul_16`` on ``weight`` as it is."""
 
     @staticmethod
-    def forward(ctx, h, weight, bias, k, fused=False, weight_grad_16=False):
+    def forward(ctx, h, weight, bias, k, fused=False, weight_grad_16=False, input_grad_16=False):
         if fused:
             sp_data, sp_index = ops.linear_topk(
                 ops._rows_in_place(h), ops._rows_in_place(weight),
@@ -80,6 +82,7 @@ class LinearMaxKFunction(torch.autograd.Function):
         ctx.save_for_backward(h, weight, sp_index)
         ctx.bias_dtype = None if bias is None else bias.dtype
         ctx.weight_grad_16 = weight_grad_16
+        ctx.input_grad_16 = input_grad_16
         ctx.mark_non_differentiable(sp_index)
         return sp_data, sp_index
 
@@ -91,7 +94,10 @@ class LinearMaxKFunction(torch.autograd.Function):
         need = ctx.needs_input_grad
         grad_h = grad_w = grad_b = None
         if need[0]:
-            grad_h = ops.cbsr_matmul(grad_data, sp_index, ops._rows_in_place(weight.float()))
+            if ctx.input_grad_16:  # no f32 copy of weight, no f32 [N, D_in], no cast pass
+                grad_h = ops.cbsr_matmul_16(grad_data, sp_index, ops._rows_in_place(weight))
+            else:
+                grad_h = ops.cbsr_matmul(grad_data, sp_index, ops._rows_in_place(weight.float()))
         if need[1] or need[2]:
             if ctx.weight_grad_16:  # no f32 copy of h: both operands go to the matrix cores
                 res = ops.cbsr_weight_grad_16(grad_data, sp_index, ops._rows_in_place(h),
@@ -104,11 +110,12 @@ class LinearMaxKFunction(torch.autograd.Function):
             grad_h = None if grad_h is None else grad_h.to(h.dtype)
             grad_w = None if grad_w is None else grad_w.to(weight.dtype)
             grad_b = None if grad_b is None else grad_b.to(ctx.bias_dtype)
-        return grad_h, grad_w if need[1] else None, grad_b, None, None, None
+        return grad_h, grad_w if need[1] else None, grad_b, None, None, None, None
 
 
 def linear_maxk(h: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], k: int,
-                mode: str = "exact", fused: bool = False, weight_grad_16: bool = False):
+                mode: str = "exact", fused: bool = False, weight_grad_16: bool = False,
+                input_grad_16: bool = False):
     """``(sp_data, sp_index) = maxk(F.linear(h, weight, bias), k)`` for ``weight [D, D_in]``,
     differentiable in ``h``, ``weight`` and ``bias``. ``mode="ref_compat"`` is refused: its padding
     slots carry no gradient, which takes the rule of the scatter (``autograd._mask_padding``).
@@ -127,7 +134,11 @@ def linear_maxk(h: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tens
     step repeats bit for bit. Its price is one more rounding: the gradient of each kept value is
     rounded to the inputs' dtype before it is multiplied with ``h`` (the products are then exact in
     f32 and the f32 sum keeps ``(n + 2) 2^-24 sum |terms|`` against the exact sum over the rounded
-    values), where the default multiplies the f32 gradient."""
+    values), where the default multiplies the f32 gradient. ``input_grad_16=True`` (16-bit inputs
+    only, else ``ValueError``) does the same for ``grad_h``: ``ops.cbsr_matmul_16`` on ``weight`` as
+    it is returns it in the inputs' dtype, the f32 sum of exact products rounded once, with no f32
+    copy of ``weight``, no f32 ``[N, D_in]`` and no cast pass, at the same price of one rounding
+    of the gradient of each kept value."""
     if mode != "exact":
         raise ValueError(f'linear_maxk supports mode="exact" only, got {mode!r}: the padding '
                          "slots of ref_compat need the MaxK scatter's rule")
@@ -137,4 +148,8 @@ def linear_maxk(h: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tens
     if weight_grad_16 and h.dtype not in ops.LINEAR_TOPK_DTYPES:
         raise ValueError(f"weight_grad_16=True needs bfloat16 or float16 inputs, got {h.dtype}: "
                          "the f32 weight gradient is ops.cbsr_weight_grad")
-    return LinearMaxKFunction.apply(h, weight, bias, k, bool(fused), bool(weight_grad_16))
+    if input_grad_16 and h.dtype not in ops.LINEAR_TOPK_DTYPES:
+        raise ValueError(f"input_grad_16=True needs bfloat16 or float16 inputs, got {h.dtype}: "
+                         "the f32 input gradient is ops.cbsr_matmul")
+    return LinearMaxKFunction.apply(h, weight, bias, k, bool(fused), bool(weight_grad_16),
+                                    bool(input_grad_16))

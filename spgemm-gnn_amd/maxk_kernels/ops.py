@@ -1429,6 +1429,39 @@ def cbsr_weight_grad_16(sp_data, sp_index, g, dim_origin: int, with_sum: bool = 
     return (grad_table, grad_sum) if with_sum else grad_table
 
 
+def cbsr_matmul_16_tile(dim_origin: int, dim_m: int) -> Tuple[int, ...]:
+    """``(depth of the product, panel width, panels, rows per tile, most work-groups along the rows
+    of a panel, LDS bytes)`` of ``maxk_cbsr_matmul_16`` for a ``[dim_origin, dim_m]`` table
+    (``maxk_cbsr_matmul_16_tile``)."""
+    return _int32_list(lib.maxk_cbsr_matmul_16_tile, int(dim_origin), int(dim_m))
+
+
+def cbsr_matmul_16(sp_data, sp_index, table, out=None, out_dtype=None) -> torch.Tensor:
+    """``densify(sp_data.to(table.dtype), sp_index) @ table`` on the matrix cores: ``[N, M]`` from
+    the CBSR tables ``[N, k]`` (f32 values, rounded to the type of ``table`` before the product)
+    and ``table`` bf16 or f16 ``[D, M]`` (``maxk_cbsr_matmul_16``: f32 sums of exact products in a
+    fixed order, distinct selectors within a row). The result is of ``out_dtype``: the table's type
+    (default; the f32 sum rounded once) or ``torch.float32``. ``out``: the tensor to write into,
+    which then sets ``out_dtype``. Rows of every argument may be strided."""
+    code = LINEAR_TOPK_DTYPES.get(table.dtype) if isinstance(table, torch.Tensor) else None
+    _need(code is not None, "table must be bfloat16 or float16")
+    dev = sp_data.device if isinstance(sp_data, torch.Tensor) else None
+    n, k, ds, is_ = _heads_tables(sp_data, sp_index, dev)
+    d, m, ts = _rows(table, "table", None, None, "dim_origin, dim_m", dev, table.dtype)
+    _need(1 <= k <= d <= 256 and m >= 1, "k must be between 1 and input dimension")
+    if out_dtype is None:
+        out_dtype = out.dtype if isinstance(out, torch.Tensor) else table.dtype
+    _need(out_dtype in (torch.float32, table.dtype), "out_dtype must be float32 or the table's dtype")
+    if out is None:
+        out = torch.empty((n, m), dtype=out_dtype, device=dev)
+    os_ = _rows(out, "out", n, m, "num_rows, dim_m", dev, out_dtype)[2]
+    with _device(dev):
+        check(lib.maxk_cbsr_matmul_16(_p(sp_data), ds, _p(sp_index), is_, _p(table), ts, code,
+                                      _p(out), os_, 0 if out_dtype == torch.float32 else code,
+                                      n, d, k, m, _stream()), "cbsr_matmul_16")
+    return out
+
+
 # -------------------------------------------------------------------------------------
 # Max aggregation (include/maxk_hip.h, "Max aggregation")
 # -------------------------------------------------------------------------------------

@@ -42,6 +42,10 @@ formula (the SSpMM backward) as a registered derivative.
                                      densify(sp_data.to(g.dtype), sp_index).T @ g and its column
                                      sums for a bf16 / f16 g, on the matrix cores; no derivative
 
+    torch.ops.maxk.cbsr_matmul_16(sp_data, sp_index, table) -> out [N, M] of the table's dtype:
+                                     densify(sp_data.to(table.dtype), sp_index) @ table for a bf16 /
+                                     f16 table [D, M], on the matrix cores; no derivative
+
     torch.ops.maxk.csr_transpose(ptr, idx, val (or None), num_cols)
                                   -> (ptr_t [num_cols + 1], idx_t [E], order [E], val_t [E], all
                                      int32 but the f32 val_t, which is empty without val): A^T of a
@@ -344,6 +348,20 @@ def cbsr_weight_grad_16(sp_data: torch.Tensor, sp_index: torch.Tensor, g: torch.
 def _(sp_data, sp_index, g, dim_origin):
     return (g.new_empty((dim_origin, g.shape[1]), dtype=torch.float32),
             g.new_empty((dim_origin,), dtype=torch.float32))
+
+
+# The 16-bit input gradient of linear_maxk(..., fused=True, input_grad_16=True)
+# (ops.cbsr_matmul_16). It is itself a backward: no derivative is registered.
+@torch.library.custom_op(f"{_NS}::cbsr_matmul_16", mutates_args=())
+def cbsr_matmul_16(sp_data: torch.Tensor, sp_index: torch.Tensor,
+                   table: torch.Tensor) -> torch.Tensor:
+    """``out [N, M]`` of the table's dtype."""
+    return ops.cbsr_matmul_16(sp_data, sp_index, table)
+
+
+@cbsr_matmul_16.register_fake
+def _(sp_data, sp_index, table):
+    return table.new_empty((sp_data.shape[0], table.shape[1]))
 
 
 # A^T of a CSR graph (ops.csr_transpose). The output shapes follow from the input shapes and

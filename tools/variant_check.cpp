@@ -39,6 +39,12 @@
 // the widths of M around the panel edges and both types, with its wave tiling, LDS plan, row
 // groups, scratch sizes and depth positions); its names are
 // tests/golden/kernel_instantiations_weight_grad16.txt.
+//
+//   variant_check matmul16
+//
+// does it for the table of csrc/variants_matmul16.h (the 16-bit CBSR product over every D, the
+// widths of M around the panel edges and both types, with its LDS plan, row groups and the two
+// placements); its names are tests/golden/kernel_instantiations_matmul16.txt.
 #include <algorithm>
 #include <climits>
 #include <cstdio>
@@ -50,6 +56,7 @@
 #include "variants_linear.h"
 #include "variants_linear_topk.h"
 #include "variants_linear_topk16.h"
+#include "variants_matmul16.h"
 #include "variants_transpose.h"
 #include "variants_weight_grad16.h"
 
@@ -286,12 +293,59 @@ static int check_weight_grad16() {
   return finish();
 }
 
+// The table of variants_matmul16.h: every D, M up to past three wide panels and both types; the
+// panels cover M without an empty one, a wave's 16 rows times the panel are whole pairs of 16 x 16
+// tiles, one work-group fits the LDS with every row 16-byte aligned, the row groups stay within
+// kGroups over all panels with no group left without a tile, and the placements of features and
+// columns are the permutations that the transposing read and the 8-column stores want.
+static int check_matmul16() {
+  using namespace maxk_mm16;
+  {
+    Family fam("matmul16", kMatmul16Variants);
+    for (int d = 1; d <= 256; ++d)
+      for (int m = 1; m <= 400; ++m)
+        for (int dt : {kBf16, kF16}) {
+          const Matmul16Variant v = select_matmul16_variant(d, m, dt);
+          fam.selected(v);
+          const int dp = padded_dim(d), mp = panel_width(m);
+          const long long p = panel_count(m);
+          bool ok = v.dp == dp && v.mp == mp && v.dtype == dt && dp >= d &&
+                    (dp == 64 || dp / 2 < d) && (mp == 64 || mp == 128) && p * mp >= m &&
+                    (p - 1) * mp < m && (mp / 16) % 2 == 0 && dp % kStep == 0 &&
+                    lds_bytes(dp, mp) <= kCuLdsBytes && waves_per_simd(dp, mp) == 2 &&
+                    (2 * (mp + kTPad)) % 16 == 0 && (2 * (dp + kAPad)) % 16 == 0 &&
+                    kTileRows * kSlotLanes == kThreads;
+          for (long long n : {0ll, 1ll, 128ll, 129ll, 32768ll, 32769ll, 232965ll, 2449029ll}) {
+            const long long w = row_groups(n, p), tiles = (n + kTileRows - 1) / kTileRows;
+            ok = ok && w >= 1 && w * p <= (p > kGroups ? p : kGroups) &&
+                 w <= (tiles > 0 ? tiles : 1) && w <= group_cap(p);
+          }
+          if (!ok) {
+            std::fprintf(stderr, "matmul16: bad tile plan for D = %d, M = %d\n", d, m);
+            g_bad = 1;
+          }
+        }
+  }
+  for (int r = 0; r < kStep; ++r) {
+    const int pos = depth_position(r), q = pos / 8, e = pos % 8;
+    const int col = staged_column(r), h = col / 16, cq = col % 16 / 4, cr = col % 4;
+    // lane (i, q) holds positions 8 q + e: features 4 q + e of the first read, 16 + 4 q + e - 4 of
+    // the second; register cr of lane group cq in tile h is column 8 cq + 4 h + cr
+    if (r != (e < 4 ? 4 * q + e : 16 + 4 * q + e - 4) || r != 8 * cq + 4 * h + cr) {
+      std::fprintf(stderr, "matmul16: feature / column %d sits at %d / %d\n", r, pos, col);
+      g_bad = 1;
+    }
+  }
+  return finish();
+}
+
 int main(int argc, char** argv) {
   if (argc > 1 && std::strcmp(argv[1], "transpose") == 0) return check_transpose();
   if (argc > 1 && std::strcmp(argv[1], "linear") == 0) return check_linear();
   if (argc > 1 && std::strcmp(argv[1], "linear_topk") == 0) return check_linear_topk();
   if (argc > 1 && std::strcmp(argv[1], "linear_topk16") == 0) return check_linear_topk16();
   if (argc > 1 && std::strcmp(argv[1], "weight_grad16") == 0) return check_weight_grad16();
+  if (argc > 1 && std::strcmp(argv[1], "matmul16") == 0) return check_matmul16();
   const bool tf[] = {false, true};
   {
     Family fam("forward", kFwdVariants);
